@@ -10,10 +10,22 @@ N x 1 GiB bucket, the C4 sharding; no collective on the encode path).
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches N worker processes itself (torchrun on
 127.0.0.1, before this process touches the GPU); under torchrun (the driver's launch) it is one of the ranks.
 
-Extra objects on the same JSON line (they never change `value`):
+A plain run does only what the headline needs: set up, warm up, time the steps, write the outputs (--dump-outputs) and
+print the line. Besides metric / value / unit / ms_per_step it carries two objects computed from the timed steps' own
+HIP events (no launches of their own):
   roofline          the encode kernel's HIP-event time vs the HBM roofline (read-only bytes per BASELINE.md, and
                     read + write), traffic = rocprofv3 PMC bytes per launch from profiles/ (traffic_source names it)
   per_launch_ms     first / median / max kernel time over the timed steps (the clock ramps under a burst of launches)
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step's encode returned (rank 0's codec.Encoded)
+as float64 .npy files, so that two builds can be compared output for output (the inputs are seeded):
+  DIR/stream_word_index.npy   which 64-bit stream words were kept: all of them up to DUMP_WORDS, else a seeded
+                              stratified sample of DUMP_WORDS words over the whole stream (ascending)
+  DIR/stream_u32.npy          those words as (k, 2) unsigned 32-bit halves (low, high), exact in float64
+  DIR/bits.npy                the stream's bit count
+
+--full adds every other measurement and check to the same JSON line (they never change `value`):
+  roofline.copy_ceiling_*  the encoder's access pattern without the coding (k_copy_pattern1d), same protocol
   steady_state      the same kernel after >= 0.25 s of back-to-back launches
   N > 1:  encode_allgather (C4 exchange: encode + RCCL all-gather of the compressed shards, gathered stream checked
           against the oracle on sampled ranges of every shard), subgroups (1/2/4/.. ranks over dist.new_group),
@@ -45,6 +57,7 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md chip table); 6.
 N_VALUES = 256 * 1024 * 1024
 SEED = 0x67636F77
 METRIC = "GiB/s device-resident fp32->ZFP encode, 256Mi-float bucket, 1/2/4/8 GPU"
+DUMP_WORDS = 1 << 20  # --dump-outputs keeps at most this many stream words (24 MiB of float64 in all)
 
 
 def parse(argv=None):
@@ -56,16 +69,26 @@ def parse(argv=None):
     ap.add_argument("--values", type=int, default=N_VALUES)
     ap.add_argument("--strong-gib", type=float, default=8.0, help="C4 strong-scaling bucket (GiB of fp32)")
     ap.add_argument("--c5-values", type=int, default=N_VALUES, help="bf16 values per rank in the c5_sharded leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: copy ceiling, steady state, the config / host / "
+                         "multi-GPU legs with their oracle checks, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the config / host / multi-GPU legs")
     ap.add_argument("--stub", action="store_true",
                     help="harness self-test on CPU: gloo, a trivial step instead of the encode (tests only)")
     ap.add_argument("--stub-mismatch", action="store_true",
                     help="stub mode: report a failed oracle check (tests that the run then exits non-zero)")
     ap.add_argument("--multi-legs", action="store_true",
                     help="run the N > 1 legs (exchange, subgroups, strong, c5_sharded) even at N = 1, over a one-rank "
-                         "RCCL group (tests: exercises the multi-GPU code on a one-GPU box)")
-    return ap.parse_args(argv)
+                         "RCCL group (tests: exercises the multi-GPU code on a one-GPU box); needs --full")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.multi_legs and not (args.full or args.stub):
+        ap.error("--multi-legs selects legs of a --full run")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------ launcher
@@ -200,6 +223,35 @@ def load_pmc_traffic(kernel_substr: str, workload: str):
             if d.get("workload") == workload and kernel_substr in d.get("kernel", ""):
                 return d.get("hbm_bytes_per_launch"), "profiles/" + f
     return None, None
+
+
+# ------------------------------------------------------------------------------------------------------ outputs
+def dump_word_index(nwords: int):
+    """The stream words --dump-outputs keeps: every word of a stream of at most DUMP_WORDS words, else one word drawn
+    from each of DUMP_WORDS equal strata of the stream (seeded: the same words on every run and build)."""
+    import numpy as np
+    if nwords <= DUMP_WORDS:
+        return np.arange(nwords, dtype=np.int64)
+    stride = nwords // DUMP_WORDS
+    rng = np.random.default_rng(SEED)
+    return np.arange(DUMP_WORDS, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_WORDS, dtype=np.int64)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Write each array as path/<name>.npy in float64 (every value dumped here is an integer below 2^53: exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
+def dump_encoded(path: str, e) -> None:
+    """--dump-outputs for a codec.Encoded: the (sampled) stream words as 32-bit halves, their positions, the bit
+    count."""
+    import numpy as np
+    idx = dump_word_index(e.nwords)
+    words = e.stream()[torch.from_numpy(idx).to(e.words.device)].cpu().numpy().view(np.uint32).reshape(-1, 2)
+    dump_outputs(path, {"stream_word_index": idx, "stream_u32": words, "bits": np.array([e.bits])})
 
 
 # ------------------------------------------------------------------------------------------------------ oracle checks
@@ -927,8 +979,12 @@ def stub_worker(ctx: Ctx):
     """Harness self-test (tests/test_bench_launcher.py): the same timing / max-over-ranks / JSON path with a trivial
     CPU step."""
     t = torch.ones(1 << 12)
-    wall, _ = timed(ctx, lambda: t.sum(), ctx.args.warmup, ctx.args.steps)
+    calls = []
+    wall, _ = timed(ctx, lambda: calls.append(t.sum()), ctx.args.warmup, ctx.args.steps)
     wall = ctx.max_over_ranks([wall])[0]
+    if ctx.args.dump_outputs and ctx.rank == 0:
+        dump_outputs(ctx.args.dump_outputs, {"stub_sum": calls[-1].reshape(1).numpy(),
+                                             "stub_calls": [len(calls)]})
     me = [ctx.rank, ctx.local, ctx.world, os.environ.get("GCOW_BENCH_LAUNCHER", "torchrun"),
           os.environ.get("MASTER_ADDR"), os.environ.get("MASTER_PORT")]
     ranks = [None] * ctx.world
@@ -961,6 +1017,9 @@ def worker(args):
     step_ms, per = timed(ctx, lambda: enc(x, stream), args.warmup, args.steps, stream=stream)
     kern_ms = sum(per) / len(per)
     step_ms, kern_ms = ctx.max_over_ranks([step_ms, kern_ms])
+    if args.dump_outputs and rank == 0:
+        # the Encoder's preallocated output: what the last timed step wrote and returned
+        dump_encoded(args.dump_outputs, codec.Encoded(enc.words, enc.bits_dev, enc.shape, p))
 
     in_bytes = n * 4
     out_bytes = n * args.rate / 8
@@ -972,63 +1031,67 @@ def worker(args):
     roofline["traffic"] = traffic
     # committed rocprofv3 --pmc pass (FETCH_SIZE + WRITE_SIZE per launch of this kernel and workload); not this run
     roofline["traffic_source"] = src
-    if p.maxbits in (32, 64):
-        # measured device-copy ceiling of the encoder's own access pattern (BASELINE.md:59): the same grid, loads and
-        # stores without the coding (k_copy_pattern1d), same protocol, right after the headline
-        cp_out = torch.empty(n // 4 * p.maxbits // 64 + 1, dtype=torch.int64, device=ctx.dev)
-        _, cper = timed(ctx, lambda: codec.copy_pattern(x, cp_out, p.maxbits, stream), args.warmup, args.steps,
-                        stream=stream)
-        ck = ctx.max_over_ranks([sum(cper) / len(cper)])[0]
-        # flat scalars (the driver's record keeps scalar fields of `roofline`, not nested objects)
-        roofline["copy_ceiling_kernel"] = "k_copy_pattern1d"
-        roofline["copy_ceiling_ms"] = round(ck, 5)
-        roofline["copy_ceiling_frac"] = round(in_bytes / (ck / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
-        roofline["copy_ceiling_frac_read_write"] = round((in_bytes + out_bytes) / (ck / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
-        roofline["kernel_over_copy_ceiling"] = round(kern_ms / ck, 4)
-        del cp_out
+    cpu = None
     extra = {"per_launch_ms": {"first": round(per[0], 4), "median": round(statistics.median(per), 4),
                                "min": round(min(per), 4), "max": round(max(per), 4)}}
-    # the same kernel once the clock has settled under load (>= 0.25 s of back-to-back launches)
-    t_end = time.perf_counter() + 0.25
-    while time.perf_counter() < t_end:
-        for _ in range(50):
-            enc(x, stream)
-        ctx.sync()
-    s_ms, sper = timed(ctx, lambda: enc(x, stream), 0, 200, stream=stream)
-    sk = sum(sper) / len(sper)
-    s_ms, sk = ctx.max_over_ranks([s_ms, sk])
-    extra["steady_state"] = {"ms_per_step": round(s_ms, 5), "GiBps": round(world * gib(in_bytes, s_ms), 2),
-                             "kernel_ms": round(sk, 5), "frac": round(in_bytes / (sk / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
-                             "frac_read_write": round((in_bytes + out_bytes) / (sk / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)}
+    if args.full:
+        if p.maxbits in (32, 64):
+            # measured device-copy ceiling of the encoder's own access pattern (BASELINE.md:59): the same grid, loads
+            # and stores without the coding (k_copy_pattern1d), same protocol, right after the headline
+            cp_out = torch.empty(n // 4 * p.maxbits // 64 + 1, dtype=torch.int64, device=ctx.dev)
+            _, cper = timed(ctx, lambda: codec.copy_pattern(x, cp_out, p.maxbits, stream), args.warmup, args.steps,
+                            stream=stream)
+            ck = ctx.max_over_ranks([sum(cper) / len(cper)])[0]
+            # flat scalars (the driver's record keeps scalar fields of `roofline`, not nested objects)
+            roofline["copy_ceiling_kernel"] = "k_copy_pattern1d"
+            roofline["copy_ceiling_ms"] = round(ck, 5)
+            roofline["copy_ceiling_frac"] = round(in_bytes / (ck / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
+            roofline["copy_ceiling_frac_read_write"] = round((in_bytes + out_bytes) / (ck / 1e3) / 1e9
+                                                             / HBM_PEAK_GBPS, 4)
+            roofline["kernel_over_copy_ceiling"] = round(kern_ms / ck, 4)
+            del cp_out
+        # the same kernel once the clock has settled under load (>= 0.25 s of back-to-back launches)
+        t_end = time.perf_counter() + 0.25
+        while time.perf_counter() < t_end:
+            for _ in range(50):
+                enc(x, stream)
+            ctx.sync()
+        s_ms, sper = timed(ctx, lambda: enc(x, stream), 0, 200, stream=stream)
+        sk = sum(sper) / len(sper)
+        s_ms, sk = ctx.max_over_ranks([s_ms, sk])
+        extra["steady_state"] = {"ms_per_step": round(s_ms, 5), "GiBps": round(world * gib(in_bytes, s_ms), 2),
+                                 "kernel_ms": round(sk, 5),
+                                 "frac": round(in_bytes / (sk / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
+                                 "frac_read_write": round((in_bytes + out_bytes) / (sk / 1e3) / 1e9 / HBM_PEAK_GBPS,
+                                                          4)}
 
-    if not args.no_extras:
-        if world > 1 or ctx.group:
-            extra["encode_allgather"] = leg_c4_exchange(ctx, lambda t: enc(t, stream), x, p, n, out_bytes)
-            torch.cuda.empty_cache()
-            extra["subgroups"] = leg_subgroups(ctx, p, n)
-            torch.cuda.empty_cache()
-            del x, enc
-            torch.cuda.empty_cache()
-            extra["strong"] = leg_strong(ctx, p, int(args.strong_gib * (1 << 30)) // 4)
-            extra["c5_sharded"] = leg_c5_sharded(ctx, args.c5_values)
-            torch.cuda.empty_cache()
-            extra["hook_exchange"] = leg_hook_exchange(ctx, args.c5_values)
-        else:
-            # the device legs first: the host paths' PCIe-bound phases leave the GPU idle and its clocks low for
-            # whatever cold leg follows them
-            extra["configs"] = leg_configs(ctx)
-            extra["host_e2e"] = leg_host_e2e(ctx, lambda t: enc(t, stream), x, p, n, in_bytes, out_bytes)
+        if not args.no_extras:
+            if world > 1 or ctx.group:
+                extra["encode_allgather"] = leg_c4_exchange(ctx, lambda t: enc(t, stream), x, p, n, out_bytes)
+                torch.cuda.empty_cache()
+                extra["subgroups"] = leg_subgroups(ctx, p, n)
+                torch.cuda.empty_cache()
+                del x, enc
+                torch.cuda.empty_cache()
+                extra["strong"] = leg_strong(ctx, p, int(args.strong_gib * (1 << 30)) // 4)
+                extra["c5_sharded"] = leg_c5_sharded(ctx, args.c5_values)
+                torch.cuda.empty_cache()
+                extra["hook_exchange"] = leg_hook_exchange(ctx, args.c5_values)
+            else:
+                # the device legs first: the host paths' PCIe-bound phases leave the GPU idle and its clocks low for
+                # whatever cold leg follows them
+                extra["configs"] = leg_configs(ctx)
+                extra["host_e2e"] = leg_host_e2e(ctx, lambda t: enc(t, stream), x, p, n, in_bytes, out_bytes)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            if "x" not in locals():
-                x = torch.empty(n, dtype=torch.float32, device=ctx.dev)
-                codec.fill_normal(x, 1e-3, seed=SEED, inject=True)
-            cpu, extra["cpu_baseline_legs"] = cpu_baseline(x, args.rate, ctx.dev)
-        except Exception as ex:  # the GPU measurement stands on its own
-            cpu = {"error": repr(ex)}
-            print("bench.py: cpu_baseline failed: %r" % (ex,), file=sys.stderr)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                if "x" not in locals():
+                    x = torch.empty(n, dtype=torch.float32, device=ctx.dev)
+                    codec.fill_normal(x, 1e-3, seed=SEED, inject=True)
+                cpu, extra["cpu_baseline_legs"] = cpu_baseline(x, args.rate, ctx.dev)
+            except Exception as ex:  # the GPU measurement stands on its own
+                cpu = {"error": repr(ex)}
+                print("bench.py: cpu_baseline failed: %r" % (ex,), file=sys.stderr)
 
     line = None
     if rank == 0:
@@ -1040,6 +1103,7 @@ def worker(args):
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(step_ms, 5),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -91,3 +91,46 @@ def test_launcher_lets_torchrun_pick_the_port():
     assert "--standalone" in cmd and "--local-addr=127.0.0.1" in cmd and "--nproc-per-node=8" in cmd
     assert not any(a.startswith("--master-port") for a in cmd)
     assert cmd[-2:] == ["--gpus", "8"]
+
+
+def test_dump_outputs_writes_last_step_as_float_npy(tmp_path):
+    """--dump-outputs DIR: after the timed steps the last step's outputs are written as DIR/<name>.npy in float64, the
+    same from run to run; --steps sets the number of timed steps (the stub counts its calls: warmup + steps)."""
+    import numpy as np
+    seen = []
+    for run in ("a", "b"):
+        out = tmp_path / run / "nested"
+        d = _run("--gpus", "1", "--steps", "5", "--dump-outputs", str(out))
+        assert d["steps"] == 5 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["stub_calls.npy", "stub_sum.npy"]
+        arrs = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert arrs["stub_sum.npy"].tolist() == [4096.0] and arrs["stub_calls.npy"].tolist() == [1.0 + 5.0]
+        seen.append(arrs)
+    assert all(np.array_equal(seen[0][f], seen[1][f]) for f in seen[0])
+
+
+def test_dump_word_index_is_a_fixed_sample():
+    """Streams up to DUMP_WORDS words are dumped whole; longer ones as one seeded word per stratum: ascending, in
+    range, spread over the whole stream, the same on every call, and within the 64 MB budget as float64."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.dump_word_index(1000), np.arange(1000))
+    assert np.array_equal(bench.dump_word_index(bench.DUMP_WORDS), np.arange(bench.DUMP_WORDS))
+    for nwords in (bench.DUMP_WORDS + 1, 3 * bench.DUMP_WORDS + 17, 64 * bench.DUMP_WORDS):
+        idx = bench.dump_word_index(nwords)
+        assert idx.size == bench.DUMP_WORDS and idx.dtype == np.int64
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < nwords
+        assert idx[-1] >= (nwords // bench.DUMP_WORDS) * (bench.DUMP_WORDS - 1)
+        assert np.array_equal(idx, bench.dump_word_index(nwords))
+    assert bench.DUMP_WORDS * 8 * 3 + 8 <= 64 * 1000 * 1000  # index + two 32-bit halves per word + bits
+
+
+def test_multi_legs_needs_full():
+    """The multi-GPU legs belong to --full: asking for them on a plain run is a usage error, not a silent no-op."""
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse(["--multi-legs"])
+    assert bench.parse(["--multi-legs", "--full"]).full and not bench.parse([]).full

@@ -555,12 +555,12 @@ def test_bench_multi_legs_world1(gc):
     """bench.py's multi-GPU legs (C4 exchange with the oracle check of the gathered stream, the sub-communicator
     curve, strong scaling, C5 sharded with the stitch checked against the oracle, the hook exchange in both forms)
     run on the GPU over a one-rank RCCL
-    group (--multi-legs), small sizes: the code the driver's 8-GPU run executes, exercised on a one-GPU box."""
+    group (--full --multi-legs), small sizes: the code the driver's 8-GPU run executes, exercised on a one-GPU box."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--multi-legs", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--multi-legs", "--steps", "3", "--warmup", "1",
            "--values", str(1 << 22), "--strong-gib", "0.0625", "--c5-values", str(1 << 22), "--no-cpu-baseline"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -577,3 +577,45 @@ def test_bench_multi_legs_world1(gc):
     for mode in ("rate16", "acc1e-6"):  # the DDP hook's exchange: all-gather form vs sharded receive
         h = d["hook_exchange"][mode]
         assert h["sharded_equals_allgather"] is True and h["sharded_mean_matches_oracle"] is True, h
+
+
+def test_bench_plain_run_dumps_the_last_step(gc, orc, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone -- none of the --full legs, no CPU baseline --
+    and --dump-outputs writes the last timed step's stream: every dumped word and the bit count equal the oracle's
+    encode of the same seeded bucket. 8 Mi + 44 values: a 2 Mi-word stream, so the dump is the seeded sample."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = (1 << 23) + 44
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--values", str(n), "--dump-outputs", str(out)]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["n_gpus"] == 1
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    # value is the bucket's GiB over ms_per_step; the line rounds ms_per_step to 5 places and value to 3
+    ms = d["ms_per_step"]
+    assert ms > 0 and abs(d["value"] - n * 4 / (ms / 1e3) / 2 ** 30) <= d["value"] * 1e-5 / ms + 1e-3
+    assert d["cpu_baseline"] is None and "copy_ceiling_ms" not in d["roofline"]
+    assert not {"steady_state", "configs", "host_e2e", "cpu_baseline_legs", "encode_allgather"} & set(d)
+
+    x = torch.empty(n, dtype=torch.float32, device="cuda")
+    gc.fill_normal(x, 1e-3, seed=0x67636F77, inject=True)
+    w_ref, bits_ref = orc.compress(x.cpu().numpy(), orc.rate(16, 1))
+    assert sorted(os.listdir(out)) == ["bits.npy", "stream_u32.npy", "stream_word_index.npy"]
+    idx, u32, bits = (np.load(out / f) for f in ("stream_word_index.npy", "stream_u32.npy", "bits.npy"))
+    assert idx.dtype == u32.dtype == bits.dtype == np.float64
+    assert idx.nbytes + u32.nbytes + bits.nbytes <= 64 * 1000 * 1000
+    assert bits.tolist() == [float(bits_ref)]
+    idx = idx.astype(np.int64)
+    assert idx.size == 1 << 20 and np.all(np.diff(idx) > 0) and idx[-1] < w_ref.size
+    got = u32.astype(np.uint64)
+    assert u32.shape == (idx.size, 2) and np.array_equal(got[:, 0] | (got[:, 1] << np.uint64(32)), w_ref[idx])

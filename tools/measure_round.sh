@@ -19,5 +19,5 @@ timeout -s KILL 120 rocprofv3 --pmc $SQ -d $O/c5_sq -o pmc --output-format csv -
 python tools/pmc_summary.py $O/c5_sq > $O/${TAG}_c5_sq_counters.json
 cp $O/${TAG}_pmc_traffic.json $O/${TAG}_c2_kernel_stats.csv $O/${TAG}_c5_acc*_pmc_traffic.json profiles/ 2>/dev/null || true
 cp $O/${TAG}_kernel_stats.csv profiles/${TAG}_c2_kernel_stats.csv 2>/dev/null || true
-timeout -k 10 300 python bench.py > $O/m_bench.log 2>&1
+timeout -k 10 300 python bench.py --full > $O/m_bench.log 2>&1
 echo measure_round done
