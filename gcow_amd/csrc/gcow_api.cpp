@@ -3,7 +3,7 @@
 // Part 1 keeps fpgasystems/gcow's sw/ call surface (sw/include/{types,zfp,stream,encode,decode}.h) with the same
 // names, struct layouts, argument meaning and return values; the codec work behind it runs on the GPU through the
 // device API of Part 2. There is no CPU codec here: host code only moves bytes (H<->D copies, stream bookkeeping,
-// block gathers) and launches the gfx950 kernels in gcow_kernels.hip.
+// block gathers) and launches the gfx950 kernels behind kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>

@@ -1,6 +1,6 @@
 // gcow_blocks.hip -- the 2-D / 3-D block kernels (one block per lane): tiles encoder instantiations, fixed-rate 3-D
 // encoder / decoder, the generic and LDS-staged decoders, and their launchers. A translation unit of its own so the
-// heavy 64-coefficient instantiations compile in parallel with gcow_kernels.hip.
+// heavy 64-coefficient instantiations compile in parallel with the 1-D and 4-D units.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -78,28 +78,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GCOW_E3F_WA
 // loop-carried state next to the 64 coefficients (152-179 VGPRs against 113 for one block), one tile per workgroup
 // does not, and 32 Ki workgroups for a 512^3 field still fill the chip.
 //   k_count3d   block lengths (closed form, codec_device.h block_length) summed per tile -> sums[tile]
-//   k_scan_ranges (gcow_kernels.hip) turns the sums into tile bit offsets and zeroes the words two tiles share
+//   k_scan_ranges (scan_stitch.hip) turns the sums into tile bit offsets and zeroes the words two tiles share
 //   k_encode3d_var  re-derives the coefficients (the lengths come from k_count3d through the workspace), a wave
 //                   prefix sum places each block in an LDS window
 //                   of the tile, the plane coder ORs the block's bits in, and the window is stored coalesced (the two
 //                   edge words shared with the neighbouring tiles by atomicOr).
 // MASK: some block may hit the bit budget (exceeded_maxbits for maxprec), so writes are clipped at the block's end
 // (LdsWriter); otherwise every block writes exactly its length and the unclipped OrWriter is used.
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane)
-{
-#if GCOW_DPP_SCAN
-  (void)lane;
-  return wave_incl_scan_dpp(x);
-#else
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    x += lane >= (uint32_t)o ? y : 0u;
-  }
-  return x;
-#endif
-}
-
 template <int DT>
 __global__ __launch_bounds__(64) void k_count3d(FieldDesc F, Params p, uint64_t* __restrict__ sums,
                                                 uint16_t* __restrict__ lens)
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(64) void k_encode3d_var(FieldDesc F, Params p, cons
   const bool valid = b < F.nblocks;
   // placement first (lengths from the count pass), so the 64 coefficients are live only from gather to code
   const uint32_t len = valid ? lens[b] : 0u;
-  const uint32_t incl = wave_incl_scan(len, lane);
+  const uint32_t incl = wave_incl_scan_dpp(len);
   const uint32_t excl = incl - len, total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
   const uint64_t base = rbase[blockIdx.x];
   const uint32_t lb = (uint32_t)(base & 31);
@@ -325,21 +310,21 @@ static hipError_t launch_tiles23_t(const FieldDesc& F, const Params& p, const Ti
   return hipGetLastError();
 }
 
+#define GCOW_TILES(D, T)                                                                                          \
+  return bf ? launch_tiles23_t<D, DT_BF16, T>(F, p, plan, out32, ws_sums, ws_base, d_total, index, index_shift, d_base, st) \
+            : launch_tiles23_t<D, DT_F32, T>(F, p, plan, out32, ws_sums, ws_base, d_total, index, index_shift, d_base, st)
 hipError_t launch_encode_tiles23(const FieldDesc& F, const Params& p, const TilePlan& plan, uint32_t* out32,
                                  uint64_t* ws_sums, uint64_t* ws_base, uint64_t* d_total, uint64_t* index,
                                  uint32_t index_shift, const uint64_t* d_base, void* stream)
 {
   hipStream_t st = hip_stream(stream);
   const bool bf = F.dtype == DT_BF16;
-#define GCOW_TILES(D, T)                                                                                          \
-  return bf ? launch_tiles23_t<D, DT_BF16, T>(F, p, plan, out32, ws_sums, ws_base, d_total, index, index_shift, d_base, st) \
-            : launch_tiles23_t<D, DT_F32, T>(F, p, plan, out32, ws_sums, ws_base, d_total, index, index_shift, d_base, st)
   if (F.dims == 2) {
     if (plan.threads == 256) { GCOW_TILES(2, 256); } else { GCOW_TILES(2, 64); }
   }
   GCOW_TILES(3, 64);
-#undef GCOW_TILES
 }
+#undef GCOW_TILES
 
 hipError_t launch_decode(const FieldDesc& F, const Params& p, const uint64_t* in, const uint64_t* index,
                          uint32_t chunk, uint64_t nchunks, bool fixed, uint64_t base_bits, uint64_t* end_out,
@@ -386,11 +371,11 @@ bool fixed3d_ok(uint32_t maxbits)
   return maxbits % 32 == 0 && (w == 2 || w == 4 || w == 8 || w == 16 || w == 32 || w == 64);
 }
 
+#define GCOW_E3(W) return bf ? launch_enc3d_t<DT_BF16, W>(F, p, out32, st) : launch_enc3d_t<DT_F32, W>(F, p, out32, st)
 hipError_t launch_encode3d_fixed(const FieldDesc& F, const Params& p, uint32_t* out32, void* stream)
 {
   hipStream_t st = hip_stream(stream);
   const bool bf = F.dtype == DT_BF16;
-#define GCOW_E3(W) return bf ? launch_enc3d_t<DT_BF16, W>(F, p, out32, st) : launch_enc3d_t<DT_F32, W>(F, p, out32, st)
   switch (p.maxbits / 32) {
     case 2: GCOW_E3(2);
     case 4: GCOW_E3(4);
@@ -399,9 +384,9 @@ hipError_t launch_encode3d_fixed(const FieldDesc& F, const Params& p, uint32_t* 
     case 32: GCOW_E3(32);
     case 64: GCOW_E3(64);
   }
-#undef GCOW_E3
   return hipErrorInvalidValue;
 }
+#undef GCOW_E3
 
 hipError_t launch_decode3d_fixed(const FieldDesc& F, const Params& p, const uint32_t* in32, void* stream)
 {

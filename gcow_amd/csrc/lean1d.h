@@ -1,6 +1,7 @@
-// lean1d.h -- pieces of the 1-D closed-form coder shared by the fixed-rate kernels (gcow_kernels.hip) and the
-// single-pass variable-rate encoder (var1d.hip): the plane / plane-pair code tables, the all-INT_MIN ("tiny")
-// payload, the byte-indexed spread tables that build the 16-plane window, and opaque v_cvt / v_ffbh wrappers.
+// lean1d.h -- pieces of the 1-D closed-form coder shared by the fixed-rate encoder (enc_fixed1d.hip) and the
+// variable-rate encoders (range form: enc1d_range.hip; tile and single-pass forms: var1d.hip): the plane / plane-pair
+// code tables, the all-INT_MIN ("tiny") payload, the byte-indexed spread tables that build the 16-plane window, and
+// opaque v_cvt / v_ffbh wrappers.
 // Embedded coder semantics: sw/src/encode.c:279-339 (4-value blocks).
 #pragma once
 

@@ -32,17 +32,10 @@
 #include "lean1d.h"
 #include "tiles.h"
 
-namespace gcow {
-
+// ---- tunables (A/B builds: tools/build_variant.sh, tools/ubench/var1d_ablate.sh)
 #ifndef GCOW_V1T
-#define GCOW_V1T 256
+#define GCOW_V1T 256  // lanes per workgroup (512 measured neutral: profiles/r06_c5_t512_negative.log)
 #endif
-constexpr uint32_t V1T = GCOW_V1T;                           // lanes per workgroup
-constexpr uint32_t V1U = 4;                                  // consecutive blocks per lane
-constexpr uint32_t V1TILE = V1T * V1U;                       // blocks per tile
-constexpr uint32_t V1MAXB = 140;                             // 9 + 3 + 4 * 32: the longest 1-D block
-constexpr uint32_t V1Q = (V1TILE * V1MAXB + 63) / 64 + 2;    // LDS window, 64-bit words
-constexpr uint64_t V1VAL = (1ull << 62) - 1;                 // status word: flag << 62 | value
 // V1_ABLATE (measurement builds only, tools/ubench/var1d_ablate.sh; 0 in the product): 1 = no look-back (tile t at
 // t * 64 Ki bits), 2 = no coding (zero codes / prepared words, lengths kept), 4 = no window store, 8 = no pair loop,
 // 16 = no prepare in the tile coder (raw words as coefficients), 32 = no length computation in the tile count,
@@ -51,6 +44,18 @@ constexpr uint64_t V1VAL = (1ull << 62) - 1;                 // status word: fla
 #ifndef V1_ABLATE
 #define V1_ABLATE 0
 #endif
+#ifndef V1_COUNT_PF
+#define V1_COUNT_PF 1  // tiles of loads in flight ahead of the counted one (k_count1d_var_tile), 1 .. 3
+#endif
+
+namespace gcow {
+
+constexpr uint32_t V1T = GCOW_V1T;                           // lanes per workgroup
+constexpr uint32_t V1U = 4;                                  // consecutive blocks per lane
+constexpr uint32_t V1TILE = V1T * V1U;                       // blocks per tile
+constexpr uint32_t V1MAXB = 140;                             // 9 + 3 + 4 * 32: the longest 1-D block
+constexpr uint32_t V1Q = (V1TILE * V1MAXB + 63) / 64 + 2;    // LDS window, 64-bit words
+constexpr uint64_t V1VAL = (1ull << 62) - 1;                 // status word: flag << 62 | value
 constexpr uint32_t V1SPIN = 96;  // polls (~1.5 us each) of a missing predecessor before computing its total here
 
 // v_lshlrev_b32 as an opaque instruction: the shift count's low 5 bits (a count of 32 shifts by 0, not UB)
@@ -128,7 +133,7 @@ __device__ __forceinline__ uint32_t v1_prep(const float* f, int cexp, int maxpre
 // A block's code (sw/src/encode.c:457-495 + :279-339) OR-ed into the lane's bit accumulator at bit `fill`, its full
 // 64-bit words stored to the window: c = the first 128 bits of the code of every plane -- the code of planes 31 ..
 // kmin is a prefix of it, so the coder ignores kmin and the length cuts it. Same evaluation as the fixed-rate lean-6
-// coder (gcow_kernels.hip): header | one '0' per empty plane above M0 | group phase through the pair table, two
+// coder (enc_fixed1d.hip): header | one '0' per empty plane above M0 | group phase through the pair table, two
 // planes per wave-uniform step, until no lane of the wave has a coded group plane left | the rest of the 32-plane
 // window verbatim from the lane's nibble jl. special: the block needs the generic coder (a group phase past the
 // 16-plane window, a group code of 64 bits or more, a code past 128 bits); its bits are left zero here.
@@ -559,9 +564,6 @@ hipError_t launch_encode1d_var_sp(const FieldDesc& F, const Params& p, uint32_t*
 //   k_encode1d_var_tile_big  the same body with the worst-case window (140 bits per block), a grid-stride loop over
 //                        the list of oversized tiles k_encode1d_var_tile appended to (the count kernel empties it).
 constexpr uint32_t V1CT = 8;                                      // tiles per count workgroup
-#ifndef V1_COUNT_PF
-#define V1_COUNT_PF 1  // tiles of loads in flight ahead of the counted one (k_count1d_var_tile), 1 .. 3
-#endif
 constexpr uint32_t V1QS = 1500 * (V1T / 256);                     // small window, qwords (95 bits per block)
 constexpr uint32_t V1TAB = 1024;                                  // pair-table rows 0..3 in LDS
 

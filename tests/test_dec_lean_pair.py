@@ -1,4 +1,4 @@
-"""Host emulation of the variable-rate lean block decoder's group phase (gcow_kernels.hip dec_block1d_lean): the
+"""Host emulation of the variable-rate lean block decoder's group phase (dec1d.h dec_block1d_lean): the
 plane-table form (one (n, 7 bits) lookup per plane) and the pair-table form (PAIR: 16-bit DecTabLP entries, up to two
 planes per (n, 10 bits) lookup, the plane table for a step that may take one plane only), each against a plain
 plane-by-plane decode of the same bits (libzfp decode_ints semantics without a budget, sw/src/decode.c:141-183). The
@@ -13,7 +13,7 @@ from test_dec_pair_fastpath import dec_pair_cx, dec_plane_cx
 M64 = (1 << 64) - 1
 
 
-def lean_pair_tab():  # gcow_kernels.hip make_dec_lean_pair
+def lean_pair_tab():  # dec1d.h make_dec_lean_pair
     t16 = []
     for t in range(3 * 1024):
         e = dec_pair_cx(t)

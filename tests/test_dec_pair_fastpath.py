@@ -1,6 +1,6 @@
-"""Host emulation of the fixed-rate 1-D two-plane decoder's fast path (gcow_kernels.hip decode_block1d_pair, 64-bit
-blocks), both step forms (GCOW_DEC_PAIR2 = 1: select-free steps; 0: the budget- and window-guarded steps), against
-the oracle's decode of the same blocks (oracle/zfp_oracle.c, libzfp decode_ints semantics, sw/src/decode.c:141-183
+"""Host emulation of the fixed-rate 1-D two-plane decoder's fast path (dec1d.h decode_block1d_pair, 64-bit
+blocks), in two step forms (select-free steps, which is what the kernel runs; and budget- and window-guarded steps,
+an independent cross-check that no longer has a product counterpart), against the oracle's decode of the same blocks (oracle/zfp_oracle.c, libzfp decode_ints semantics, sw/src/decode.c:141-183
 with the block-size fix). The claim checked: every block the fast path does not flag special decodes bit-exactly, on
 encoder output (the C2 distribution, wide-range and sparse blocks) and on arbitrary 64-bit words (nonzero padding,
 long group phases, plane codes crossing the budget)."""
@@ -11,7 +11,7 @@ M64 = (1 << 64) - 1
 NB = 0xAAAAAAAA
 
 
-def dec_plane_cx(t):  # gcow_kernels.hip dec_plane_cx: (n, budget bits - 1, 7 stream bits) -> nibble | len << 4 | n' << 8
+def dec_plane_cx(t):  # dec1d.h dec_plane_cx: (n, budget bits - 1, 7 stream bits) -> nibble | len << 4 | n' << 8
     n0, r, b = t >> 10, (t >> 7) & 7, t & 127
     n, bits = n0, r + 1
     if n >= 4:
@@ -38,7 +38,7 @@ def dec_plane_cx(t):  # gcow_kernels.hip dec_plane_cx: (n, budget bits - 1, 7 st
     return x | (pos << 4) | (n << 8)
 
 
-def dec_pair_cx(t):  # gcow_kernels.hip dec_pair_cx
+def dec_pair_cx(t):  # dec1d.h dec_pair_cx
     n, b = t >> 10, t & 1023
     e1 = dec_plane_cx((((n << 3) | 7) << 7) | (b & 127))
     x1, l1, n1 = e1 & 15, (e1 >> 4) & 15, e1 >> 8
@@ -65,7 +65,7 @@ def window_to_coeffs(Y, top, u):
         u[i] |= bitrev32(field) >> (31 - top)
 
 
-def gather_tab():  # gcow_kernels.hip make_gather_tab
+def gather_tab():  # dec1d.h make_gather_tab
     T = [0] * 1024
     for s in range(4):
         for b in range(256):
@@ -89,7 +89,7 @@ def perm_b32(s0, s1, sel):  # v_perm_b32 for selector bytes 0..7 and 0x0c (zero)
     return out
 
 
-def window_to_coeffs_lds(Y, top, u):  # gcow_kernels.hip window_to_coeffs_lds
+def window_to_coeffs_lds(Y, top, u):  # dec1d.h window_to_coeffs_lds
     lo, hi = Y & 0xFFFFFFFF, Y >> 32
     A = GT[lo & 255] | GT[256 + ((lo >> 8) & 255)] | GT[512 + ((lo >> 16) & 255)] | GT[768 + (lo >> 24)]
     B = GT[hi & 255] | GT[256 + ((hi >> 8) & 255)] | GT[512 + ((hi >> 16) & 255)] | GT[768 + (hi >> 24)]

@@ -189,9 +189,9 @@ def test_var1d_decode_exact_stream_buffer(gc, orc, tol, mix):
                                      (1e-6, False), (1e-6, True), (1e-9, False)])
 def test_var1d_decode_capacity_buffer_tiers(gc, orc, tol, mix):
     """The same streams decoded from the encoder's capacity-sized buffer (what a hook holds): the buffer's size says
-    nothing about the stream, so launch_decode1d_var launches the 32 / 48 / 64-bit stage tiers gated on the stream's
-    average from its own index (vdec_tier) and the second pass takes the chosen tier's overflow. Bit for bit against
-    the oracle, sparse (1e-1: ~10 bits per block) to dense (1e-9: past every stage)."""
+    nothing about the stream, so launch_decode1d_var launches the 32- and 64-bit stage tiers (the 48-bit tier exists
+    only for a buffer sized like its stream) gated on the stream's average from its own index (vdec_tier) and the
+    second pass takes the chosen tier's overflow. Bit for bit against the oracle, sparse (1e-1: ~10 bits per block) to dense (1e-9: past every stage)."""
     n = 4 * 16 * 128 * 9 + 4 * 16 * 37 + 4 * 5 + 2
     a = orc.gen_normal(n, 1e-3, 0xCA9AC + int(-np.log10(tol)), True)
     if mix:
@@ -703,8 +703,8 @@ def test_c3_full_size_roundtrip(gc, orc):
 
 def test_multichunk_fixed_rate_1d(gc, orc):
     """More than 2^27 blocks: the fixed-rate 1-D encoder and decoder launch the grid in chunks of 2^27 blocks (buffer
-    offsets stay below 2^32; gcow_kernels.hip launch_fixed1d_t / launch_decode_fixed1d), as C4's strong-scaling legs
-    do with 1-2 Gi values per rank. n = 2^29 + 4 * 1001 + 3 values (2 GiB): two chunks and a padded last block. Whole
+    offsets stay below 2^32; enc_fixed1d.hip launch_fixed1d_t / dec1d.hip launch_decode_fixed1d), as C4's
+    strong-scaling legs do with 1-2 Gi values per rank. n = 2^29 + 4 * 1001 + 3 values (2 GiB): two chunks and a padded last block. Whole
     stream and whole decode vs the threaded oracle at rates 16 and 8."""
     n = (1 << 29) + 4 * 1001 + 3
     T = min(16, os.cpu_count() or 1)

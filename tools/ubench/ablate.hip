@@ -3,7 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../gcow_amd/csrc/gcow_kernels.hip"
+#include "../../gcow_amd/csrc/enc_fixed1d.hip"
+#include "../../gcow_amd/csrc/dec1d.h"
 #include "../../gcow_amd/csrc/gcow_blocks.hip"
 #include "legacy_variants.hip"
 

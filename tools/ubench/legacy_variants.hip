@@ -1,8 +1,94 @@
-// Historical 1-D fixed-rate encoder variants (lean / lean-2 / lean-3 coders, per-lane, lockstep, persistent and
+// Historical 1-D fixed-rate encoder variants (lean .. lean-5 coders, per-lane, lockstep, persistent and
 // non-persistent kernels) kept for the ablation microbenchmark only; the product uses the one-shot
-// k_encode_fixed1d_np with the lean-5 coder (gcow_amd/csrc/gcow_kernels.hip). Included by ablate.hip after
-// gcow_kernels.hip.
+// k_encode_fixed1d_np with the lean-6 coder (gcow_amd/csrc/enc_fixed1d.hip). Included by ablate.hip after
+// enc_fixed1d.hip and dec1d.h (dswap64).
 namespace gcow {
+
+// ---- the shift/mask plane window of the lean .. lean-5 coders (lean-6 builds it from LDS tables: lean1d.h
+// window_lds), and the lean-5 coder, the product default before lean-6
+
+// 4 x 16 bit-matrix transpose in a 64-bit word: input row r = bits [16r, 16r + 16), output bit 4c + r = input
+// bit 16r + c. The index map is a rotation of the 6 index bits, done as 4 index-bit swaps (delta swaps, each one
+// 64-bit shift pair and two 3-input bit ops).
+__device__ __forceinline__ uint64_t transpose4x16(uint64_t x)
+{
+  x = dswap64(x, 0x0000AAAA0000AAAAull, 15);  // index bits 0 <-> 4
+  x = dswap64(x, 0x00000000CCCCCCCCull, 30);  // 1 <-> 5
+  x = dswap64(x, 0x0000F0F00000F0F0ull, 12);  // 2 <-> 4
+  x = dswap64(x, 0x00000000FF00FF00ull, 24);  // 3 <-> 5
+  return x;
+}
+
+// 16 bit planes starting at plane `top` going down, as nibbles: nibble j of the result = bits (top - j) of u0..u3.
+__device__ __forceinline__ uint64_t plane_window(const uint32_t* u, uint32_t sh)
+{
+  const uint32_t g0 = (__builtin_bitreverse32(u[0]) >> sh) & 0xffffu;
+  const uint32_t g1 = (__builtin_bitreverse32(u[1]) >> sh) & 0xffffu;
+  const uint32_t g2 = (__builtin_bitreverse32(u[2]) >> sh) & 0xffffu;
+  const uint32_t g3 = (__builtin_bitreverse32(u[3]) >> sh) & 0xffffu;
+  const uint64_t x = (uint64_t)(g0 | (g1 << 16)) | ((uint64_t)(g2 | (g3 << 16)) << 32);
+  return transpose4x16(x);
+}
+
+// Lean-5 block: same stream as lean-4 (and encode.c:457-495 for d = 1, fixed rate, kmin = 0).
+//  * tiny (all values cast to INT_MIN) and zero blocks are selected from constants at the end, so the cast needs
+//    no per-value range select;
+//  * pair 0 always starts at n = 0 and pair 1 is taken by ~92 % of waves: both accumulate in 32 bits (<= 28 code
+//    bits), one 64-bit shift places them; only pairs 2.. (about half the waves) use the budget-guarded 64-bit path.
+template <uint32_t WB>
+__device__ __forceinline__ uint64_t encode_block1d_lean5(const float* f, const uint32_t* tab, bool& special)
+{
+  const uint32_t a0 = __float_as_uint(f[0]) & 0x7fffffffu, a1 = __float_as_uint(f[1]) & 0x7fffffffu;
+  const uint32_t a2 = __float_as_uint(f[2]) & 0x7fffffffu, a3 = __float_as_uint(f[3]) & 0x7fffffffu;
+  const uint32_t m = max(max(a0, a1), max(a2, a3));
+  special = m >= 0x7f800000u;  // Inf or NaN present
+  const uint32_t E = m >> 23;
+  const float s = __uint_as_float((283u - E) << 23);  // 2^(30 - e); meaningless for tiny / special lanes
+  int32_t q[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] = cvt_i32_hw(f[i] * s);
+  fwd_lift(q[0], q[1], q[2], q[3]);
+  uint32_t u[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) u[i] = ((uint32_t)q[i] + 0xaaaaaaaau) ^ 0xaaaaaaaau;
+  const uint32_t o23 = u[2] | u[3];
+  const uint32_t sh = __builtin_clz(u[0] | u[1] | o23 | 1u);  // 31 - M0
+  const int M0 = 31 - (int)sh;
+  const int jg = o23 ? (int)__builtin_clz(o23) - (int)sh : M0;  // group phase: window nibbles 0 .. jg
+  const uint64_t Y = plane_window(u, sh);
+  uint32_t pos = 9 + sh;
+  uint32_t e = tab[(uint32_t)Y & 255u];
+  uint32_t G = e >> 17, gl = (e >> 13) & 15u;
+  int j = 2;
+  if (__any(jg >= 2)) {
+    e = tab5_next(tab, e, ((uint32_t)Y >> 8) & 255u);
+    G |= (e >> 17) << gl;
+    gl += (e >> 13) & 15u;
+    j = 4;
+  }
+  uint64_t acc = (2ull * E + 3ull) | ((uint64_t)G << pos);
+  pos += gl;
+#pragma unroll
+  for (int jj = 4; jj < 16; jj += 2) {
+    if (j < jj || !__any(jj <= jg)) break;
+    e = tab5_next(tab, e, (uint32_t)(Y >> (4 * jj)) & 255u);
+    const uint32_t code = pos < WB ? (e >> 17) : 0u;  // 64-bit shifts wrap: nothing past the budget
+    acc |= (uint64_t)code << pos;
+    pos += (e >> 13) & 15u;
+    j = jj + 2;
+  }
+  special = special || (jg >= 16 && pos < WB);  // group phase runs past the 16-plane window (generic coder)
+  if (j < 16 && pos < WB) acc |= (Y >> (4 * j)) << pos;  // rest of the window, verbatim
+  const uint32_t p2 = pos + 4u * (uint32_t)(16 - j);      // where plane M0 - 16 lands
+  if (__any(p2 < WB && M0 >= 16)) {
+    const uint64_t Y2 = plane_window(u, (uint32_t)max(47 - M0, 0));  // planes M0 - 16 .. M0 - 31
+    if (p2 < WB && M0 >= 16) acc |= Y2 << p2;
+  }
+  constexpr uint64_t TINY = tiny_payload_cx((int)WB - 9) << 9;
+  const uint64_t tv = m ? (TINY | (2ull * E + 3ull)) : 0ull;
+  acc = E < 29u ? tv : acc;  // zero, subnormal and tiny-normal maxima: every value casts to INT_MIN (or is 0)
+  return WB == 64 ? acc : (acc & ((1ull << WB) - 1ull));
+}
 
 // ---- the persistent grid-stride lean-5 encoder (the product kernel before the one-shot grid)
 // Persistent grid-stride encoder with NB rotating register buffers (prefetch depth NB): each step codes buffer k,
