@@ -167,6 +167,53 @@ class Encoder:
         return Encoded(self.words, self.bits_dev, self.shape, self.params, self.index, self.index_stride)
 
 
+class ResidualEncoder(Encoder):
+    """Preallocated error-feedback encoder (gcow_encode_residual_device) for a 1-D bucket of n values: calling it with
+    (x, err) codes y = x + err and leaves err = finite(y - decode(stream)) (err: fp32 device tensor of n values,
+    updated in place). Rate 8 / 16 run the fused kernel; every other parameter set is composed on the device from the
+    encoder and decoder, through a workspace held here."""
+
+    def __init__(self, n: int, dtype, params: GcowParams, device=None, index_stride: int = 0):
+        super().__init__((int(n),), dtype, params, device, index_stride)
+        f = field_of_shape(self.shape, dtype)
+        # sized from the parameters alone: nothing for the fused kernel (rate 8 / 16; a bucket or err view off 16-byte
+        # alignment is then refused by the call), the composed path's y, encoder workspace and index otherwise
+        self.ws_bytes = self.L.gcow_encode_residual_workspace_bytes(C.byref(f), C.byref(params))
+        self.ws = torch.zeros(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor, stream=None) -> Encoded:
+        if tuple(x.shape) != self.shape or x.dtype != self.dtype:
+            raise GcowError("ResidualEncoder built for %s %s, got %s %s" % (self.shape, self.dtype, tuple(x.shape),
+                                                                           x.dtype))
+        _check_err(x, err)
+        f = field_of(x)
+        st = self.L.gcow_encode_residual_device(C.byref(f), C.byref(self.params), err.data_ptr(), err.data_ptr(),
+                                                self.words.data_ptr(), self.cap,
+                                                None if self.fixed else self.bits_dev.data_ptr(), self.ws.data_ptr(),
+                                                self.ws_bytes,
+                                                self.index.data_ptr() if self.index is not None else None,
+                                                self.index_stride, _stream_ptr(stream))
+        check(st, "gcow_encode_residual_device")
+        return Encoded(self.words, self.bits_dev, self.shape, self.params, self.index, self.index_stride)
+
+
+def _check_err(x: torch.Tensor, err: torch.Tensor):
+    if not (x.is_cuda and x.dim() == 1 and x.is_contiguous()):
+        raise GcowError("encode_residual expects a contiguous 1-D device tensor")
+    if not (err.is_cuda and err.device == x.device and err.dtype == torch.float32 and err.is_contiguous()
+            and err.numel() == x.numel()):
+        raise GcowError("encode_residual: err must be a contiguous fp32 tensor of x.numel() values on x's device")
+
+
+def encode_residual(x: torch.Tensor, err: torch.Tensor, params: GcowParams, index_stride: int = 0,
+                    stream=None) -> Encoded:
+    """Error feedback: encode y = x + err (x: 1-D contiguous device tensor, fp32 or bf16; one fp32 add per value) and
+    update `err` in place to y - decode(stream), non-finite differences as 0 (gcow_encode_residual_device). The
+    stream is the one `encode` gives for the fp32 tensor y."""
+    _check_err(x, err)
+    return ResidualEncoder(x.numel(), x.dtype, params, x.device, index_stride)(x, err, stream)
+
+
 def field_of_shape(shape, dtype) -> ZfpInput:
     f = ZfpInput()
     f.dtype = DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_FLOAT

@@ -804,6 +804,99 @@ gcow_status gcow_decode_device(const zfp_input* field, const gcow_params* p, con
   return decode_impl(field, p, d_in, d_index, index_stride, 0, nullptr, hip_stream, in_bytes);
 }
 
+// ---------------------------------------------------------------------------------------------- error feedback
+static size_t align256(size_t x);
+
+// The composed path's block index when the caller gives none: one entry every 16 blocks, kept in the workspace
+static const uint32_t kResidIndexStride = 16;
+
+// The fused kernel's domain: the lean fixed-rate encoder's (launch_fixed1d_t's kmin0 branch, whole-word blocks)
+static bool resid_lean_params(const gcow_params& p)
+{
+  return p.minbits == p.maxbits && (p.maxbits == 64 || p.maxbits == 32) && p.maxprec >= 32 && p.minexp <= -154;
+}
+
+// 1-D, unit stride, fp32 / bf16; fills the fp32 field of y (data unset)
+static gcow_status resid_field(const zfp_input* field, zfp_input& yf)
+{
+  if (!field) return fail(GCOW_ERR_INVALID, "null field");
+  if (dims_of(field) != 1) return fail(GCOW_ERR_UNSUPPORTED, "encode_residual takes 1-D fields");
+  if (field->sx != 0 && field->sx != 1) return fail(GCOW_ERR_UNSUPPORTED, "encode_residual takes contiguous fields");
+  if (field->dtype != dtype_float && field->dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "encode_residual supports dtype_float and dtype_bf16");
+  std::memset(&yf, 0, sizeof(yf));
+  yf.dtype = dtype_float;
+  yf.nx = field->nx;
+  return GCOW_OK;
+}
+
+size_t gcow_encode_residual_workspace_bytes(const zfp_input* field, const gcow_params* p)
+{
+  zfp_input yf;
+  if (!p || resid_field(field, yf)) return 0;
+  gcow::FieldDesc F;
+  if (make_field(field, F, false)) return 0;
+  if (resid_lean_params(*p) && (!field->data || F.vec)) return 0;  // the fused kernel
+  const size_t idx = p->minbits == p->maxbits ? 0 : gcow_index_entries(&yf, kResidIndexStride) * 8;
+  return align256((size_t)field->nx * 4) + align256(gcow_encode_workspace_bytes(&yf, p)) + align256(idx);
+}
+
+gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_params* p, const float* d_err_in,
+                                        float* d_err_out, void* d_out, size_t out_capacity, uint64_t* d_total_bits,
+                                        void* d_workspace, size_t workspace_bytes, uint64_t* d_index,
+                                        uint32_t index_stride, void* hip_stream)
+{
+  zfp_input yf;
+  gcow_status st = resid_field(field, yf);
+  if (st) return st;
+  gcow::FieldDesc F;
+  if ((st = make_field(field, F, false))) return st;
+  if ((st = check_params(p, 1))) return st;
+  if (!d_err_out) return fail(GCOW_ERR_INVALID, "null d_err_out");
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if (((uintptr_t)d_err_in | (uintptr_t)d_err_out) % 4) return fail(GCOW_ERR_INVALID, "misaligned error buffer");
+  if (out_capacity < gcow_max_output_bytes(field, p))
+    return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_max_output_bytes()");
+  if (d_index && (!index_stride || index_stride > 256 || (index_stride & (index_stride - 1))))
+    return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+  if (F.nblocks == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  const gcow::Params pp = P(*p);
+  const bool rows16 = (((uintptr_t)d_err_in | (uintptr_t)d_err_out) % 16) == 0;
+  if (resid_lean_params(*p) && fast1d_ok(F, *p, d_index) && rows16) {
+    GCOW_HIP(gcow::launch_encode_resid1d(F.data, (int)F.dtype, F.n[0], pp, d_err_in, d_err_out, d_out, hip_stream));
+    if (p->maxbits == 32 && (F.nblocks & 1))  // stream_flush: zero the upper half of the last word
+      GCOW_HIP(hipMemsetAsync((uint32_t*)d_out + F.nblocks, 0, 4, (hipStream_t)hip_stream));
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, (uint64_t)F.nblocks * p->maxbits, hip_stream));
+    return GCOW_OK;
+  }
+  // composed: y = x + e in the workspace, the encoders on y, the decoder into d_err_out, e' = finite(y - decode)
+  const bool fixed = p->minbits == p->maxbits;
+  const size_t ybytes = align256((size_t)field->nx * 4), ews = gcow_encode_workspace_bytes(&yf, p);
+  const size_t idxb = fixed ? 0 : gcow_index_entries(&yf, kResidIndexStride) * 8;
+  if (!d_workspace || workspace_bytes < ybytes + align256(ews) + align256(idxb))
+    return fail(GCOW_ERR_INVALID, "workspace smaller than the composed path needs (gcow_encode_residual_workspace_bytes() "
+                                  "of a field whose data pointer is set; error buffers off 16-byte alignment take "
+                                  "this path at every parameter set)");
+  float* y = (float*)d_workspace;
+  void* enc_ws = (char*)d_workspace + ybytes;
+  if (!fixed && !d_index) {
+    d_index = (uint64_t*)((char*)d_workspace + ybytes + align256(ews));
+    index_stride = kResidIndexStride;
+  }
+  GCOW_HIP(gcow::launch_resid_form(F.data, (int)F.dtype, F.n[0], d_err_in, y, hip_stream));
+  yf.data = y;
+  if ((st = encode_impl(&yf, p, d_out, out_capacity, d_total_bits, enc_ws, ews, d_index, index_stride, hip_stream)))
+    return st;
+  zfp_input ef = yf;
+  ef.data = d_err_out;  // e_in was consumed above: e_out may alias it
+  if ((st = decode_impl(&ef, p, d_out, d_index, index_stride, 0, nullptr, hip_stream, out_capacity))) return st;
+  GCOW_HIP(gcow::launch_resid_finish(y, d_err_out, F.n[0], hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

@@ -88,6 +88,13 @@ size_t var1d_tile_workspace_bytes(uint64_t nblocks);
 hipError_t launch_encode1d_var_tile(const FieldDesc& F, const Params& p, uint32_t* out32, uint64_t* ws,
                                     uint64_t* d_total, uint64_t* index, uint32_t index_shift, const uint64_t* d_base,
                                     void* stream);
+// Error feedback (enc_resid1d.hip). Fused: the lean fixed-rate domain (maxbits 64 / 32, maxprec >= 32, minexp <= -154),
+// contiguous 16-byte aligned rows; y = x + e_in (e_in null: zeros) is coded to out and e_out = finite(y - decode);
+// e_in == e_out allowed. Composed path: y = x + e_in, then e = finite(y - e) on a buffer that holds the decode.
+hipError_t launch_encode_resid1d(const void* in, int dtype, uint64_t nvals, const Params& p, const float* e_in,
+                                 float* e_out, void* out, void* stream);
+hipError_t launch_resid_form(const void* in, int dtype, uint64_t nvals, const float* e_in, float* y, void* stream);
+hipError_t launch_resid_finish(const float* y, float* e, uint64_t nvals, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

@@ -16,6 +16,10 @@ All register with `ddp_model.register_comm_hook(make_hook_state(hook=hook, ...),
 hook: the state's exchange group is created by `GcowHookState.setup()`, a collective every rank calls at the same
 point). `GcowHookState.codec` defaults to the
 device codec (gcow_amd.dist.DeviceCodec); tests inject an oracle-backed codec to run the hook bodies over gloo.
+
+Error feedback (`GcowHookState.error_feedback`, both wire hooks): what the codec truncates from a rank's bucket is
+kept on that rank and added to its next step's bucket before encoding, so the sent gradients average over steps to
+the meant ones (one fused kernel at rate 8 / 16: codec.encode_residual).
 """
 import contextlib
 import queue
@@ -51,7 +55,16 @@ class GcowHookState:
     Failure: a rank whose exchange raises stops its comm thread (that bucket's future and every later one fail at
     once) and aborts the exchange group. Over gloo that closes the connections and peers blocked in an exchange
     collective error out at once; over RCCL/NCCL a peer already blocked in a collective only fails when `timeout_s`
-    expires (the communicator's watchdog then tears the process group -- and by default the process -- down)."""
+    expires (the communicator's watchdog then tears the process group -- and by default the process -- down).
+
+    `error_feedback` (compressed_allgather_hook, compressed_sharded_hook): each rank keeps e = y - decode(encode(y))
+    of what it sent (y = its gradient bucket + the e of the step before) and encodes with codec.encode_residual. The
+    state holds one fp32 buffer per bucket, zero-initialised, keyed by the bucket's index and numel: a bucket whose
+    size changed (DDP rebuilds its buckets after the first iteration) drops the old buffer and starts from zeros
+    again. Buckets of equal size that the rebuild permutes are not told apart -- one step's error of the other bucket
+    is then added once; `reset_error_feedback()` after the first iteration avoids it. roundtrip_hook raises ValueError
+    with the flag set: its loss is applied after the reduction, identically on every rank. Unset (the default):
+    nothing changes and encode_residual is never called."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -59,9 +72,12 @@ class GcowHookState:
     # the state is registered with compressed_sharded_hook (its exchange runs on the comm thread at any rate); set by
     # make_hook_state(hook=compressed_sharded_hook)
     sharded: bool = False
+    # error feedback for the wire hooks (class docstring); roundtrip_hook refuses it
+    error_feedback: bool = False
     _worker: object = field(default=None, repr=False)
     _side: dict = field(default_factory=dict, repr=False)
     _comm_group: object = field(default=None, repr=False)
+    _errors: dict = field(default_factory=dict, repr=False)
 
     def get_codec(self):
         return self.codec or gdist.device_codec()
@@ -112,6 +128,19 @@ class GcowHookState:
             except Exception:  # noqa: BLE001
                 pass
 
+    def error_buffer(self, index, x: torch.Tensor) -> torch.Tensor:
+        """The carried error of bucket `index` for the flattened bucket x: fp32, x.numel() values on x's device, zeros
+        at first use and whenever the bucket's size (or device) differs from the buffer kept -- the old one is dropped."""
+        e = self._errors.get(index)
+        if e is None or e.numel() != x.numel() or e.device != x.device:
+            e = self._errors[index] = torch.zeros(x.numel(), dtype=torch.float32, device=x.device)
+        return e
+
+    def reset_error_feedback(self):
+        """Forget every carried error (the next step starts from zeros): after loading a checkpoint, changing the
+        codec parameters, or skipping a step whose gradients were discarded."""
+        self._errors.clear()
+
     def side_stream(self, dev):
         if dev not in self._side:
             self._side[dev] = torch.cuda.Stream(dev)
@@ -146,8 +175,20 @@ def _mean_into(cdc, flat: torch.Tensor, *args):
         flat.copy_(cdc.decode_mean(*args).to(flat.dtype))
 
 
+def _encode(state: GcowHookState, cdc, bucket, x: torch.Tensor, stride: int, slot):
+    """The wire hooks' encode of the flattened bucket x: with state.error_feedback, of x plus the bucket's carried error,
+    which is updated in place (the buffer lives on the state, so the exchange never reads it)."""
+    if not state.error_feedback:
+        return cdc.encode(x, state.params, stride, slot=slot)
+    index = bucket.index() if hasattr(bucket, "index") else None
+    return cdc.encode_residual(x, state.error_buffer(index, x), state.params, stride, slot=slot)
+
+
 def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
     """Mean all-reduce, then the lossy encode -> decode the reference applies (zfpy), device-resident."""
+    if state.error_feedback:
+        raise ValueError("error_feedback is for the wire hooks (compressed_allgather_hook, compressed_sharded_hook): "
+                         "roundtrip_hook applies its loss after the reduction, identically on every rank")
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -233,7 +274,7 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     cdc = state.get_codec()
     slot = bucket.index() if hasattr(bucket, "index") else None
     if _codec.is_fixed(p):
-        words, _, _ = cdc.encode(x, p, 0, slot=slot)
+        words, _, _ = _encode(state, cdc, bucket, x, 0, slot)
         nw = ((n + 3) // 4 * p.maxbits + 63) // 64
         gathered = torch.zeros(world * nw + 2, dtype=torch.int64, device=x.device)
         fut = gdist.allgather_into_async(gathered[: world * nw], words[:nw].contiguous(), group)
@@ -249,7 +290,7 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
 
         return fut.then(finish)
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    words, bits, index8 = cdc.encode(x, p, SHARDED_INDEX_STRIDE, slot=slot)
+    words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot)
     index = cdc.pack_index16(index8, n, p)  # what travels: one entry per 16 blocks
     dev = x.device
     if dev.type == "cuda":
@@ -306,7 +347,7 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     stride = 0 if fixed else SHARDED_INDEX_STRIDE
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
     slot = ("sharded", bucket.index() if hasattr(bucket, "index") else None)
-    words, bits, index = cdc.encode(x, p, stride, slot=slot)
+    words, bits, index = _encode(state, cdc, bucket, x, stride, slot)
     dev = x.device
     if dev.type == "cuda":
         ev = torch.cuda.Event()

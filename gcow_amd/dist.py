@@ -45,19 +45,32 @@ class DeviceCodec:
         """-> (words int64 tensor, bits int64[1] tensor on x.device, block index or None). Calls with the same shape,
         params and `slot` reuse (overwrite) one set of output buffers; callers whose streams are still in flight on
         another stream pass distinct slots (the DDP hook: one per bucket)."""
-        from . import codec
         x = x.reshape(-1)
+        e = self._encoder(x, params, index_stride, slot, False)(x if x.is_contiguous() else x.contiguous())
+        return e.words, e.bits_dev, e.index
+
+    def encode_residual(self, x: torch.Tensor, err: torch.Tensor, params, index_stride: int = 0, slot=None):
+        """Error feedback: `encode` of y = x + err, with `err` (fp32, x.numel() values, on x's device) updated in place
+        to y - decode(stream) (codec.encode_residual). Same return value and cache policy as `encode`; the encoders
+        are cached apart from `encode`'s (they hold the composed path's workspace)."""
+        x = x.reshape(-1)
+        e = self._encoder(x, params, index_stride, slot, True)(x if x.is_contiguous() else x.contiguous(), err)
+        return e.words, e.bits_dev, e.index
+
+    def _encoder(self, x, params, index_stride, slot, residual):
+        from . import codec
         self._tick += 1
-        key = (slot, x.numel(), x.dtype, x.device, params.tuple(), index_stride)
+        key = (slot, x.numel(), x.dtype, x.device, params.tuple(), index_stride) + (("residual",) if residual else ())
         ent = self._enc.get(key)
         if ent is None:
-            ent = self._enc[key] = [codec.Encoder((x.numel(),), x.dtype, params, x.device, index_stride), self._tick]
+            enc = codec.ResidualEncoder(x.numel(), x.dtype, params, x.device, index_stride) if residual else \
+                codec.Encoder((x.numel(),), x.dtype, params, x.device, index_stride)
+            ent = self._enc[key] = [enc, self._tick]
         else:
             ent[1] = self._tick
             self._enc.move_to_end(key)
         self._evict_idle()
-        e = ent[0](x if x.is_contiguous() else x.contiguous())
-        return e.words, e.bits_dev, e.index
+        return ent[0]
 
     def _evict_idle(self):
         limit = self.idle_factor * len(self._enc) + self.idle_slack

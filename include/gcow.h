@@ -237,6 +237,35 @@ gcow_status gcow_encode_device_append(const zfp_input* field, const gcow_params*
                                       void* hip_stream);
 
 /*
+ * Error feedback: gcow_encode_device of a 1-D bucket plus the carried compression error, which also writes the new
+ * error. field->data: DEVICE, 1-D, contiguous, n values, fp32 or bf16. d_err_in: DEVICE fp32, n values, or NULL (all
+ * zeros). d_err_out: DEVICE fp32, n values; d_err_in == d_err_out (in place) is allowed and gives the same result.
+ *   1. y[i] = (float)x[i] + e_in[i]: one IEEE fp32 add, round to nearest, denormals kept.
+ *   2. d_out receives the stream of the fp32 array y under p, byte-identical to gcow_encode_device of y (a bf16
+ *      bucket is coded as the fp32 y, not as bf16). d_total_bits, d_index / index_stride as in gcow_encode_device.
+ *   3. yhat = the libzfp 0.5.5 decode of that stream (what gcow_decode_device returns).
+ *   4. r[i] = y[i] - yhat[i]: one IEEE fp32 subtract; e_out[i] = r[i] when r[i] is finite, else +0.0f, so that a NaN or
+ *      Inf gradient (an AMP overflow step) or an overflowing x + e does not stay in the carried error.
+ * The padding values of a partial last block give no residual: nothing is written past e_out[n - 1], nor past the
+ * stream's flushed words. Over steps the sent values then average to the meant ones: sum_t yhat_t = sum_t x_t + e_0 - e_T.
+ * Fixed rate with whole-word blocks (minbits == maxbits in {32, 64}, maxprec >= 32, minexp <= -154; rate 8 and 16),
+ * 16-byte aligned rows and no d_index: one fused kernel (each block coded, its word decoded in registers, both outputs
+ * stored: 14 bytes of HBM traffic per fp32 value at rate 16), no workspace. Every other 1-D parameter set (and a lean
+ * call with d_index, or with buffers off 16-byte alignment) is composed from the existing kernels: y into the
+ * workspace, the encoders on y, the decoder into d_err_out, r in place; a variable-rate stream is decoded through the
+ * caller's block index, or (d_index NULL) through one every 16 blocks kept in the workspace.
+ * gcow_encode_residual_workspace_bytes covers y, the encoder's workspace and that index (0 for the fused kernel;
+ * decided from p and, when field->data is set, its alignment). Capacity and workspace checks as gcow_encode_device.
+ * Asynchronous on hip_stream; no host synchronisation, no allocation.
+ * GCOW_ERR_UNSUPPORTED: dims != 1, a non-unit stride, a dtype other than float / bf16. GCOW_ERR_INVALID: NULL d_err_out.
+ */
+size_t gcow_encode_residual_workspace_bytes(const zfp_input* field, const gcow_params* p);
+gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_params* p, const float* d_err_in,
+                                        float* d_err_out, void* d_out, size_t out_capacity, uint64_t* d_total_bits,
+                                        void* d_workspace, size_t workspace_bytes, uint64_t* d_index,
+                                        uint32_t index_stride, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by
