@@ -214,6 +214,33 @@ def encode_residual(x: torch.Tensor, err: torch.Tensor, params: GcowParams, inde
     return ResidualEncoder(x.numel(), x.dtype, params, x.device, index_stride)(x, err, stream)
 
 
+def roundtrip(x: torch.Tensor, params: GcowParams, out: torch.Tensor | None = None, bits: torch.Tensor | None = None,
+              stream=None) -> torch.Tensor:
+    """decode(encode(x, params)) in one kernel, without the stream (gcow_roundtrip_device): what the reference's
+    training loop does to its flattened gradients. x: contiguous 1-D (or flattened-contiguous) fp32 / bf16 device
+    tensor. out: fp32 or bf16 tensor of x.numel() values (default: a new tensor of x's dtype; out=x runs in place; a
+    bf16 out is the fp32 decode rounded to nearest even). bits: optional int64[1] device tensor that receives the bit
+    length `encode` would report, for callers that log the compression ratio. Returns out."""
+    if not (x.is_cuda and x.is_contiguous() and x.dim() >= 1):
+        raise GcowError("roundtrip expects a contiguous device tensor")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("roundtrip: dtype %s not supported (float32, bfloat16)" % x.dtype)
+    if out is None:
+        out = torch.empty_like(x)
+    if not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.numel() == x.numel()
+            and out.dtype in (torch.float32, torch.bfloat16)):
+        raise GcowError("roundtrip: out must be a contiguous fp32 or bf16 tensor of x.numel() values on x's device")
+    if bits is not None and not (bits.is_cuda and bits.device == x.device and bits.dtype == torch.int64
+                                 and bits.numel() == 1):
+        raise GcowError("roundtrip: bits must be a one-element int64 tensor on x's device")
+    f = field_of(x.view(-1))
+    st = load().gcow_roundtrip_device(C.byref(f), C.byref(params), out.data_ptr(),
+                                      DTYPE_BF16 if out.dtype == torch.bfloat16 else DTYPE_FLOAT,
+                                      bits.data_ptr() if bits is not None else None, _stream_ptr(stream))
+    check(st, "gcow_roundtrip_device")
+    return out
+
+
 def field_of_shape(shape, dtype) -> ZfpInput:
     f = ZfpInput()
     f.dtype = DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_FLOAT

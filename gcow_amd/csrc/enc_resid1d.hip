@@ -20,35 +20,13 @@
 #include "kernels.h"
 #include "lean1d.h"
 #include "pipe.h"
+#include "regbits.h"
 
 #ifndef GCOW_EF_U
 #define GCOW_EF_U 8  // blocks per lane: 2 U rows in flight (64 VGPRs at U = 8, fp32)
 #endif
 
 namespace gcow {
-
-// The word a block was just coded to, read back by the generic decoder (the decoders' special lanes): the stream
-// store is non-temporal and not visible yet, so the word comes from the register. Bits past the word read as zero;
-// the block's budget (maxbits) keeps the decoder inside it.
-struct RegReader64 {
-  uint64_t w;
-  uint32_t pos;
-  __device__ __forceinline__ uint64_t peek64() const { return pos < 64u ? w >> pos : 0ull; }
-  __device__ __forceinline__ uint64_t get(uint32_t n)
-  {
-    if (!n) return 0;
-    const uint64_t v = peek64() & lowmask64(n);
-    pos += n;
-    return v;
-  }
-  __device__ __forceinline__ uint32_t bit()
-  {
-    const uint32_t b = (uint32_t)peek64() & 1u;
-    pos++;
-    return b;
-  }
-  __device__ __forceinline__ void skip(uint64_t k) { pos += (uint32_t)k; }
-};
 
 // y - d as one IEEE subtract (no contraction, denormals kept); a non-finite result (NaN / Inf gradient, x + e overflow)
 // carries nothing forward

@@ -897,6 +897,47 @@ gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_param
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- fused round trip
+gcow_status gcow_roundtrip_device(const zfp_input* field, const gcow_params* p, void* d_out, data_type out_dtype,
+                                  uint64_t* d_total_bits, void* hip_stream)
+{
+  if (!field) return fail(GCOW_ERR_INVALID, "null field");
+  if (!p) return fail(GCOW_ERR_INVALID, "null params");
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if (field->ny || field->nz || field->nw) return fail(GCOW_ERR_UNSUPPORTED, "roundtrip takes 1-D fields");
+  if (field->sx != 0 && field->sx != 1) return fail(GCOW_ERR_UNSUPPORTED, "roundtrip takes contiguous fields");
+  if (field->dtype != dtype_float && field->dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip supports dtype_float and dtype_bf16 fields");
+  if (out_dtype != dtype_float && out_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip writes dtype_float or dtype_bf16");
+  gcow_status st = check_params(p, 1);
+  if (st) return st;
+  const size_t esz_in = field->dtype == dtype_bf16 ? 2 : 4, esz_out = out_dtype == dtype_bf16 ? 2 : 4;
+  if ((uintptr_t)field->data % esz_in || (uintptr_t)d_out % esz_out)
+    return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+  if ((uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "misaligned d_total_bits");
+  if (field->nx == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
+  gcow::FieldDesc F;
+  if ((st = make_field(field, F, false))) return st;
+  const bool fixed = p->minbits == p->maxbits;
+  const bool rows16 = (((uintptr_t)field->data | (uintptr_t)d_out) % 16) == 0;
+  int domain = gcow::kRoundtripGeneric;
+  if (rows16 && resid_lean_params(*p) && fast1d_ok(F, *p, nullptr)) domain = gcow::kRoundtripLean;
+  else if (rows16 && p->minbits <= 1 && p->maxbits >= 160) domain = gcow::kRoundtripVar;
+  uint64_t* total = nullptr;  // variable rate: the kernels add every block's length
+  if (d_total_bits) {
+    GCOW_HIP(gcow::launch_set_u64(d_total_bits, fixed ? (uint64_t)F.nblocks * p->maxbits : 0, hip_stream));
+    if (!fixed) total = d_total_bits;
+  }
+  GCOW_HIP(gcow::launch_roundtrip1d(F.data, (int)F.dtype, F.n[0], P(*p), domain, d_out,
+                                    out_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32, total, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

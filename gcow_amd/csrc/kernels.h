@@ -95,6 +95,13 @@ hipError_t launch_encode_resid1d(const void* in, int dtype, uint64_t nvals, cons
                                  float* e_out, void* out, void* stream);
 hipError_t launch_resid_form(const void* in, int dtype, uint64_t nvals, const float* e_in, float* y, void* stream);
 hipError_t launch_resid_finish(const float* y, float* e, uint64_t nvals, void* stream);
+// Fused round trip (roundtrip1d.hip): out = decode(encode(in)) of nvals contiguous values, no stream. domain selects
+// the kernel: Lean = the lean fixed-rate domain above, Var = minbits <= 1 and maxbits >= 160 (both need 16-byte aligned
+// in and out; the partial last block goes through the generic kernel), Generic = anything. total (optional, zeroed by
+// the caller) has every block's bit length added to it; pass null for fixed-rate sets.
+enum { kRoundtripLean = 0, kRoundtripVar = 1, kRoundtripGeneric = 2 };
+hipError_t launch_roundtrip1d(const void* in, int in_dtype, uint64_t nvals, const Params& p, int domain, void* out,
+                              int out_dtype, uint64_t* total, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

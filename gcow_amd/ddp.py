@@ -185,7 +185,8 @@ def _encode(state: GcowHookState, cdc, bucket, x: torch.Tensor, stride: int, slo
 
 
 def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
-    """Mean all-reduce, then the lossy encode -> decode the reference applies (zfpy), device-resident."""
+    """Mean all-reduce, then the lossy encode -> decode the reference applies (zfpy), device-resident: one fused
+    `roundtrip` call on an fp32 / bf16 bucket when the codec has one, else encode followed by decode."""
     if state.error_feedback:
         raise ValueError("error_feedback is for the wire hooks (compressed_allgather_hook, compressed_sharded_hook): "
                          "roundtrip_hook applies its loss after the reduction, identically on every rank")
@@ -198,6 +199,9 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
     def lossy(f):
         t = f.value()[0]
         flat, x = _flat(t)
+        if hasattr(cdc, "roundtrip") and flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous():
+            cdc.roundtrip(x, state.params, out=flat)  # one kernel, in place, no stream (same bits as the path below)
+            return t
         stride = 0 if _codec.is_fixed(state.params) else INDEX_STRIDE
         # per-bucket buffers: DDP may run several buckets' callbacks before the first one's decode has read its words
         words, _, index = cdc.encode(x, state.params, stride,

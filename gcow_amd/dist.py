@@ -88,6 +88,12 @@ class DeviceCodec:
         from . import codec
         return codec.decode(words, (n,), params, index=index, index_stride=index_stride, out=out)
 
+    def roundtrip(self, x: torch.Tensor, params, out=None):
+        """decode(encode(x)) in one kernel without the stream (codec.roundtrip): nothing cached, nothing allocated
+        when `out` is given (out=x: in place)."""
+        from . import codec
+        return codec.roundtrip(x, params, out=out)
+
     def pack_index16(self, index8, n: int, params):
         from . import codec
         return codec.pack_index16(index8, n, params)

@@ -266,6 +266,35 @@ gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_param
                                         uint32_t index_stride, void* hip_stream);
 
 /*
+ * Round trip without a stream: d_out[i] = decode(encode(field))[i], bit for bit what gcow_encode_device followed by
+ * gcow_decode_device leaves in a field of out_dtype, in one pass that writes no stream, needs no workspace and no
+ * block index -- the reference's training loop, which compresses the flattened gradients and decompresses them at
+ * once to simulate the loss (hw/models/train_imagenet.py:448-475). *d_total_bits (optional, DEVICE uint64) = what
+ * gcow_encode_device would report: the stream's bit length before stream_flush.
+ * field->data: DEVICE, 1-D, contiguous (sx 0 or 1), n values, dtype_float or dtype_bf16. d_out: DEVICE, n values of
+ * out_dtype, dtype_float or dtype_bf16 in any combination with the field's; a bf16 output is the fp32 decode rounded to
+ * nearest even, as gcow_decode_device writes a bf16 field. Nothing is written past d_out[n - 1].
+ * Aliasing: d_out == field->data is allowed when out_dtype == field->dtype (in place) and gives the same result. Any
+ * other overlap of the two buffers is undefined.
+ * Every 1-D parameter set gcow_encode_device accepts is supported, by one of three kernels:
+ *   - fixed rate with whole-word blocks (minbits == maxbits in {32, 64}, maxprec >= 32, minexp <= -154; rate 8 and
+ *     16), both buffers 16-byte aligned: each block coded and its word decoded in registers, one 16-byte (fp32) or
+ *     8-byte (bf16) row read and one written per block;
+ *   - no budget (minbits <= 1, maxbits >= 160: accuracy, precision and expert sets of that shape), both buffers
+ *     16-byte aligned: the decoded coefficients are the coded ones with the planes below the block's precision
+ *     cleared, so no embedded coder runs at all;
+ *   - everything else, buffers off 16-byte alignment, and the partial last block of the two above: one lane per block
+ *     through the generic block coder and decoder over registers.
+ * Asynchronous on hip_stream: no allocation, no host synchronisation, *d_total_bits is never read on the host. n = 0
+ * writes *d_total_bits = 0 and returns GCOW_OK.
+ * GCOW_ERR_UNSUPPORTED: dims != 1, a non-unit stride, a field dtype or out_dtype other than float / bf16.
+ * GCOW_ERR_INVALID: NULL field, p or d_out; field->data, d_out or d_total_bits misaligned for its element type;
+ * check_params as in gcow_encode_device.
+ */
+gcow_status gcow_roundtrip_device(const zfp_input* field, const gcow_params* p, void* d_out, data_type out_dtype,
+                                  uint64_t* d_total_bits, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by
