@@ -105,6 +105,7 @@ def load():
         "gcow_encode_device_append": (i32, [pi, pp, vp, sz, vp, vp, vp, sz, vp, u32, vp]),
         "gcow_encode_residual_workspace_bytes": (sz, [pi, pp]),
         "gcow_encode_residual_device": (i32, [pi, pp, vp, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
+        "gcow_encode_residual_path": (i32, [pi, pp, vp, vp, vp]),
         "gcow_roundtrip_device": (i32, [pi, pp, vp, i32, vp, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),

@@ -167,19 +167,28 @@ class Encoder:
         return Encoded(self.words, self.bits_dev, self.shape, self.params, self.index, self.index_stride)
 
 
+RESID_COMPOSED, RESID_FUSED_FIXED, RESID_FUSED_VAR = 0, 1, 2  # gcow_encode_residual_path
+
+
 class ResidualEncoder(Encoder):
     """Preallocated error-feedback encoder (gcow_encode_residual_device) for a 1-D bucket of n values: calling it with
     (x, err) codes y = x + err and leaves err = finite(y - decode(stream)) (err: fp32 device tensor of n values,
-    updated in place). Rate 8 / 16 run the fused kernel; every other parameter set is composed on the device from the
-    encoder and decoder, through a workspace held here."""
+    updated in place). `path` says how, for 16-byte aligned tensors (gcow_encode_residual_path): RESID_FUSED_FIXED at
+    rate 8 / 16 without an index (one kernel, no workspace), RESID_FUSED_VAR for accuracy, precision and expert sets
+    with minbits <= 1 and maxbits >= 160 (the variable-rate encoder's passes on y, the code pass writing err from its
+    own coefficients; the encoder's workspace), RESID_COMPOSED for everything else (encoder and decoder composed on
+    the device through a workspace that also holds y). A view off 16-byte alignment takes the composed path."""
 
     def __init__(self, n: int, dtype, params: GcowParams, device=None, index_stride: int = 0):
         super().__init__((int(n),), dtype, params, device, index_stride)
         f = field_of_shape(self.shape, dtype)
-        # sized from the parameters alone: nothing for the fused kernel (rate 8 / 16; a bucket or err view off 16-byte
-        # alignment is then refused by the call), the composed path's y, encoder workspace and index otherwise
+        # sized from the parameters alone (aligned tensors assumed): nothing for the fused fixed-rate kernel, the
+        # encoder's workspace for the fused variable-rate passes, the composed path's y, encoder workspace and index
+        # otherwise; a call whose views turn out off 16-byte alignment is refused where this is too small
         self.ws_bytes = self.L.gcow_encode_residual_workspace_bytes(C.byref(f), C.byref(params))
         self.ws = torch.zeros(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
+        self.path = self.L.gcow_encode_residual_path(C.byref(f), C.byref(params), None, None,
+                                                     self.index.data_ptr() if self.index is not None else None)
 
     def __call__(self, x: torch.Tensor, err: torch.Tensor, stream=None) -> Encoded:
         if tuple(x.shape) != self.shape or x.dtype != self.dtype:
@@ -209,7 +218,8 @@ def encode_residual(x: torch.Tensor, err: torch.Tensor, params: GcowParams, inde
                     stream=None) -> Encoded:
     """Error feedback: encode y = x + err (x: 1-D contiguous device tensor, fp32 or bf16; one fp32 add per value) and
     update `err` in place to y - decode(stream), non-finite differences as 0 (gcow_encode_residual_device). The
-    stream is the one `encode` gives for the fp32 tensor y."""
+    stream is the one `encode` gives for the fp32 tensor y. Rate 8 / 16 and the variable-rate sets without a budget
+    (accuracy, precision) run fused; see ResidualEncoder."""
     _check_err(x, err)
     return ResidualEncoder(x.numel(), x.dtype, params, x.device, index_stride)(x, err, stream)
 

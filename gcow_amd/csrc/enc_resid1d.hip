@@ -5,7 +5,8 @@
 //                           (decode_block1d_pair / _fast), e' = finite(y - decode): 16 (8) + 16 bytes read, 8 (4) + 16
 //                           written per block, where encode + decode + two torch passes move 144 (fp32, rate 16)
 //   k_encode_resid1d_tail   the partial last block
-//   k_resid_form            y = x + e               (composed path, every other 1-D parameter set)
+//   k_resid_form            y = x + e               (composed path: what neither this kernel nor the variable-rate
+//                                                   form in var1d.hip takes)
 //   k_resid_finish          e' = finite(y - decode)
 #include <hip/hip_runtime.h>
 
@@ -21,20 +22,13 @@
 #include "lean1d.h"
 #include "pipe.h"
 #include "regbits.h"
+#include "var1d_prep.h"  // resid_bits
 
 #ifndef GCOW_EF_U
 #define GCOW_EF_U 8  // blocks per lane: 2 U rows in flight (64 VGPRs at U = 8, fp32)
 #endif
 
 namespace gcow {
-
-// y - d as one IEEE subtract (no contraction, denormals kept); a non-finite result (NaN / Inf gradient, x + e overflow)
-// carries nothing forward
-__device__ __forceinline__ uint32_t resid_bits(float y, float d)
-{
-  const uint32_t r = __float_as_uint(__fsub_rn(y, d));
-  return (r & 0x7f800000u) == 0x7f800000u ? 0u : r;
-}
 
 // LDS image: the encoder's pair table and spread tables (2304 words), then the decoder's table (64-bit blocks: the pair
 // table, 12 KiB; 32-bit blocks: the plane table, 10 KiB).

@@ -830,13 +830,38 @@ static gcow_status resid_field(const zfp_input* field, zfp_input& yf)
   return GCOW_OK;
 }
 
+// The one rule behind gcow_encode_residual_path, _workspace_bytes and _device: -1 = refused, else GCOW_RESID_*.
+// Pointers are looked at for alignment only (NULL: aligned).
+static int resid_path(const zfp_input* field, const gcow_params* p, const float* d_err_in, const float* d_err_out,
+                      const uint64_t* d_index)
+{
+  zfp_input yf;
+  gcow::FieldDesc F;
+  if (resid_field(field, yf) || make_field(field, F, false) || check_params(p, 1)) return -1;
+  const uintptr_t e = (uintptr_t)d_err_in | (uintptr_t)d_err_out;
+  if (e % 4) {
+    fail(GCOW_ERR_INVALID, "misaligned error buffer");
+    return -1;
+  }
+  const bool rows16 = e % 16 == 0;
+  if (resid_lean_params(*p) && fast1d_ok(F, *p, d_index) && rows16) return GCOW_RESID_FUSED_FIXED;
+  if (p->minbits <= 1 && p->maxbits >= 160 && rows16 && (uintptr_t)field->data % 16 == 0) return GCOW_RESID_FUSED_VAR;
+  return GCOW_RESID_COMPOSED;
+}
+
+int gcow_encode_residual_path(const zfp_input* field, const gcow_params* p, const float* d_err_in,
+                              const float* d_err_out, const uint64_t* d_index)
+{
+  return resid_path(field, p, d_err_in, d_err_out, d_index);
+}
+
 size_t gcow_encode_residual_workspace_bytes(const zfp_input* field, const gcow_params* p)
 {
   zfp_input yf;
   if (!p || resid_field(field, yf)) return 0;
-  gcow::FieldDesc F;
-  if (make_field(field, F, false)) return 0;
-  if (resid_lean_params(*p) && (!field->data || F.vec)) return 0;  // the fused kernel
+  const int path = resid_path(field, p, nullptr, nullptr, nullptr);
+  if (path < 0 || path == GCOW_RESID_FUSED_FIXED) return 0;
+  if (path == GCOW_RESID_FUSED_VAR) return gcow_encode_workspace_bytes(&yf, p);  // no y, no private index
   const size_t idx = p->minbits == p->maxbits ? 0 : gcow_index_entries(&yf, kResidIndexStride) * 8;
   return align256((size_t)field->nx * 4) + align256(gcow_encode_workspace_bytes(&yf, p)) + align256(idx);
 }
@@ -864,12 +889,23 @@ gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_param
     return GCOW_OK;
   }
   const gcow::Params pp = P(*p);
-  const bool rows16 = (((uintptr_t)d_err_in | (uintptr_t)d_err_out) % 16) == 0;
-  if (resid_lean_params(*p) && fast1d_ok(F, *p, d_index) && rows16) {
+  const int path = resid_path(field, p, d_err_in, d_err_out, d_index);
+  if (path < 0) return GCOW_ERR_INVALID;  // unreachable: every refusal was returned above
+  if (path == GCOW_RESID_FUSED_FIXED) {
     GCOW_HIP(gcow::launch_encode_resid1d(F.data, (int)F.dtype, F.n[0], pp, d_err_in, d_err_out, d_out, hip_stream));
     if (p->maxbits == 32 && (F.nblocks & 1))  // stream_flush: zero the upper half of the last word
       GCOW_HIP(hipMemsetAsync((uint32_t*)d_out + F.nblocks, 0, 4, (hipStream_t)hip_stream));
     if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, (uint64_t)F.nblocks * p->maxbits, hip_stream));
+    return GCOW_OK;
+  }
+  if (path == GCOW_RESID_FUSED_VAR) {  // the tile encoder on y in registers, e' from its coefficients (var1d.hip)
+    const size_t need = gcow_encode_workspace_bytes(&yf, p);
+    if (!d_workspace || workspace_bytes < need)
+      return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_residual_workspace_bytes()");
+    uint32_t shift = 0;
+    while (d_index && (1u << shift) < index_stride) shift++;
+    GCOW_HIP(gcow::launch_encode_resid1d_var(F.data, (int)F.dtype, F.n[0], pp, d_err_in, d_err_out, (uint32_t*)d_out,
+                                             (uint64_t*)d_workspace, d_total_bits, d_index, shift, hip_stream));
     return GCOW_OK;
   }
   // composed: y = x + e in the workspace, the encoders on y, the decoder into d_err_out, e' = finite(y - decode)

@@ -93,6 +93,13 @@ hipError_t launch_encode1d_var_tile(const FieldDesc& F, const Params& p, uint32_
 // e_in == e_out allowed. Composed path: y = x + e_in, then e = finite(y - e) on a buffer that holds the decode.
 hipError_t launch_encode_resid1d(const void* in, int dtype, uint64_t nvals, const Params& p, const float* e_in,
                                  float* e_out, void* out, void* stream);
+// Fused at variable rate (var1d.hip): minbits <= 1 and maxbits >= 160, x (fp32 / bf16), e_in (or null) and e_out
+// 16-byte aligned; the tile form of the encoder on y = x + e_in, whose code pass writes e_out = finite(y - decode)
+// from the coder's own coefficients. ws = var1d_tile_workspace_bytes(), the tile form's layout; index as
+// launch_encode1d_var_tile writes it. Always the tile form: g_var1d_variant does not apply.
+hipError_t launch_encode_resid1d_var(const void* x, int x_dtype, uint64_t nvals, const Params& p, const float* e_in,
+                                     float* e_out, uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                     uint32_t index_shift, void* stream);
 hipError_t launch_resid_form(const void* in, int dtype, uint64_t nvals, const float* e_in, float* y, void* stream);
 hipError_t launch_resid_finish(const float* y, float* e, uint64_t nvals, void* stream);
 // Fused round trip (roundtrip1d.hip): out = decode(encode(in)) of nvals contiguous values, no stream. domain selects

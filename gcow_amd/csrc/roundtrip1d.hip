@@ -56,17 +56,6 @@ __device__ __forceinline__ void rt_store_row(__amdgpu_buffer_rsrc_t rout, uint32
   }
 }
 
-// Any parameter set: the block's code in three registers, decoded from them. Returns the block's bit length
-// (encode_block's return value: minbits padding and the maxbits cut included).
-__device__ __forceinline__ uint32_t rt_block_generic(const float* f, const Params& p, float* d)
-{
-  RegWriter192 wr{0ull, 0ull, 0ull, 0u};
-  const uint32_t len = encode_block<1>(wr, f, p);
-  RegReader192 rd{wr.w0, wr.w1, wr.w2};
-  decode_block<1>(rd, p, d);
-  return len;
-}
-
 // Sum v over the workgroup's 256 lanes and add it to *total: one 64-bit atomic per workgroup.
 __device__ __forceinline__ void rt_count(uint32_t v, uint32_t* sh, uint64_t* total)
 {
@@ -177,11 +166,8 @@ __global__ __launch_bounds__(256) void k_roundtrip1d_fixed_np(const void* in, ui
 }
 
 // ------------------------------------------------------------------------------------------------ (b) no budget
-// With u, K and hdr from v1_prep (K = 31 - kmin): an untruncated code holds planes 31 .. kmin of every coefficient
-// whole, so the decoder's coefficients are u_j with the planes below kmin cleared; a block whose header is the single
-// '0' bit (hdr = 0: a zero block, or no precision) decodes to +0. Then the inverse negabinary map, inv_lift and
-// dequant_scale(emax) * (float)q as decode_block has it (scale first, one multiply: a subnormal maximum decodes to
-// +-0). Same wait rule as rt_fixed_block: N = U - 1 for every block.
+// The decode is v1_decode_closed (var1d_prep.h) of what v1_prep returns; Inf / NaN blocks take rt_block_generic. Same
+// wait rule as rt_fixed_block: N = U - 1 for every block.
 template <int DT_IN, int DT_OUT, bool COUNT, int U, int K>
 __device__ __forceinline__ void rt_var_block(typename PipeRow<DT_IN>::T (&rx)[U], const Params& p, uint32_t b0,
                                              uint32_t nfull, __amdgpu_buffer_rsrc_t rout, uint32_t& lsum)
@@ -193,14 +179,7 @@ __device__ __forceinline__ void rt_var_block(typename PipeRow<DT_IN>::T (&rx)[U]
   uint32_t u[4], hdr, Kp;
   bool inf;
   uint32_t len = v1_prep(f, -122 - p.minexp, (int)min(p.maxprec, 64u), u, hdr, Kp, inf);
-  const uint32_t keep = hdr ? ~((1u << (31u - Kp)) - 1u) : 0u;
-  int32_t q[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) q[i] = (int32_t)(((u[i] & keep) ^ 0xaaaaaaaau) - 0xaaaaaaaau);
-  inv_lift(q[0], q[1], q[2], q[3]);
-  const float sc = dequant_scale((int)(hdr >> 1) - 127);  // hdr = 2 (emax + 127) + 1; hdr = 0: q = 0, any finite scale
-#pragma unroll
-  for (int i = 0; i < 4; i++) d[i] = sc * (float)q[i];
+  v1_decode_closed(u, hdr, Kp, d);
   if (inf) len = rt_block_generic(f, p, d);  // Inf / NaN present: cast and header follow the reference's integer path
   rt_store_row<DT_OUT>(rout, b, d);
   if constexpr (COUNT) lsum += b < nfull ? len : 0u;

@@ -668,12 +668,18 @@ __global__ __launch_bounds__(V1T) void k_count1d_var_tile(FieldDesc F, Params p,
 
 // One tile (raw words and the lane's byte lengths lw given) coded into the window `win`, from bit B & 127 (the
 // 16-byte stream boundary below the tile's first bit); tab / rs already in LDS. Ends with the window complete
-// (barrier) and the block index written.
-template <int DT>
+// (barrier) and the block index written. hook(k, f, u, hdr, K, inf) sees every block k of the lane once, with what
+// v1_prep returned for it (the residual form below takes its decode from there); the default does nothing.
+struct V1NoHook {
+  __device__ __forceinline__ void operator()(uint32_t, const float*, const uint32_t*, uint32_t, uint32_t, bool) const {}
+};
+
+template <int DT, class Hook = V1NoHook>
 __device__ __forceinline__ void v1_tile_code(const FieldDesc& F, const Params& p, uint32_t t, uint64_t B,
                                              const V1Raw<DT>& raw, uint32_t lw, uint64_t* __restrict__ index,
                                              uint32_t index_shift, const uint32_t* tab, const uint32_t* rs,
-                                             uint64_t* win, uint32_t* scan_sh, uint32_t* s_special)
+                                             uint64_t* win, uint32_t* scan_sh, uint32_t* s_special,
+                                             const Hook& hook = Hook())
 {
   uint32_t* win32 = (uint32_t*)win;
   const uint32_t tid = threadIdx.x;
@@ -716,6 +722,7 @@ __device__ __forceinline__ void v1_tile_code(const FieldDesc& F, const Params& p
     } else {
       (void)v1_prep(f, cexp, maxprec, u, hdr, K, inf);  // the length comes from the count pass
     }
+    hook(k, f, u, hdr, K, inf);
     bool sp = inf && bl + k < F.nblocks;
     uint64_t c0, c1;
     if constexpr ((V1_ABLATE & 2) != 0) {  // measurement builds: no coder (the prepared words stand in for the code)
@@ -957,6 +964,409 @@ hipError_t launch_encode1d_var_tile(const FieldDesc& F, const Params& p, uint32_
     k_encode1d_var_tile_big<DT_F32><<<nbig, V1T, 0, st>>>(F, p, base, lens8, out32, index, index_shift, ntiles, over);
   }
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------- tile form with the residual
+// Error feedback at variable rate (gcow_encode_residual_device, include/gcow.h): the tile form above
+// on the field y = x + e (fp32; x fp32 or bf16, e fp32 or absent), whose code pass also writes e' = finite(y - yhat).
+// yhat needs no decoder: in this domain it is v1_decode_closed of the coefficients v1_prep hands the coder anyway
+// (the hook of v1_tile_code), so the residual costs one more row read in each pass and one row written.
+//   k_count1d_var_tile_resid       k_count1d_var_tile on y: the x rows and the e rows of tile i + PF are requested
+//                                  before tile i is counted; writes lens8 / sums / gsums, nothing to e_out
+//   k_encode1d_var_tile_resid      k_encode1d_var_tile on y, plus the tile's e' rows
+//   k_encode1d_var_tile_big_resid  the oversized tiles, as k_encode1d_var_tile_big
+// e_in may be e_out: a lane reads the e rows of its own blocks only, and the e' rows it stores are those of its quad
+// of lanes (V1ResidOut::store_quad), computed from values all four have loaded -- so every row a wave writes it has
+// read before, and no other wave reads it. Every tile is coded (its e read and its e' written) exactly once, by the
+// main kernel or by the _big one: an oversized tile leaves the main kernel before any store. y = fadd(x, e) with e = +0 when e_in is null, so that -0 becomes +0
+// as in the model (tests/residual_model.py).
+#ifndef V1_RESID_PF
+#define V1_RESID_PF 1  // tiles of loads in flight ahead of the counted one (k_count1d_var_tile_resid), 1 .. 3
+#endif
+
+__device__ __forceinline__ bool v1_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// The lane's V1U blocks of y from its x words and e words
+template <int DT_X>
+__device__ __forceinline__ void v1_form_y(const V1Raw<DT_X>& rx, const V1Raw<DT_F32>& re, V1Raw<DT_F32>& y)
+{
+#pragma unroll
+  for (uint32_t k = 0; k < V1U; k++) {
+    float f[4], e[4];
+    rx.block(k, f);
+    re.block(k, e);
+    y.w[k] = make_uint4(__float_as_uint(__fadd_rn(f[0], e[0])), __float_as_uint(__fadd_rn(f[1], e[1])),
+                        __float_as_uint(__fadd_rn(f[2], e[2])), __float_as_uint(__fadd_rn(f[3], e[3])));
+  }
+}
+
+// Tile t of y through compiler-managed loads: whole 16-byte rows of a full tile, else the padded gather of x and of e
+// (the same padding indices for both, so a padding value of y is a copy of a real one).
+template <int DT_X>
+__device__ __forceinline__ void v1_load_y(const FieldDesc& F, const float* e_in, uint32_t t, V1Raw<DT_F32>& y)
+{
+  V1Raw<DT_X> rx;
+  V1Raw<DT_F32> re;
+  rx.load(F, t, F.vec && v1_aligned16(F.data));
+  if (e_in) {
+    FieldDesc Fe = F;
+    Fe.data = e_in;
+    Fe.dtype = DT_F32;
+    Fe.vec = v1_aligned16(e_in) ? 1u : 0u;
+    re.load(Fe, t, Fe.vec != 0);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < V1U; k++) re.w[k] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  v1_form_y<DT_X>(rx, re, y);
+}
+
+// wait until at most N vector memory operations are outstanding; ties the tile's x and e words to after the wait
+template <int N, int NX>
+__device__ __forceinline__ void v1_wait_xe(v1_u4 (&x)[NX], v1_u4 (&e)[V1U])
+{
+  if constexpr (NX == 2)
+    asm volatile("s_waitcnt vmcnt(%6)"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3])
+                 : "n"(N)
+                 : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(%8)"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3])
+                 : "n"(N)
+                 : "memory");
+}
+
+// the same for k tiles still in flight, NX x loads and (HASE) V1U e loads each
+template <int NX, bool HASE>
+__device__ __forceinline__ void v1_wait_tiles_xe(v1_u4 (&x)[NX], v1_u4 (&e)[V1U], uint32_t k)
+{
+  if constexpr (HASE) {
+    constexpr int NT = NX + (int)V1U;
+    switch (k) {
+      case 0: v1_wait_xe<0, NX>(x, e); break;
+      case 1: v1_wait_xe<NT, NX>(x, e); break;
+      case 2: v1_wait_xe<2 * NT, NX>(x, e); break;
+      default: v1_wait_xe<3 * NT, NX>(x, e); break;
+    }
+  } else {
+    v1_wait_tiles<NX>(x, k);
+  }
+}
+
+template <int DT_X, bool HASE>
+__global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid(FieldDesc F, Params p, const float* e_in,
+                                                                uint32_t ntiles, uint64_t* __restrict__ sums,
+                                                                uint32_t* __restrict__ lens8,
+                                                                uint32_t* __restrict__ nover,
+                                                                uint64_t* __restrict__ gsums)
+{
+  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
+  // k_count1d_var_tile's shape. Loads per lane and tile, in issue order: NX x rows (fp32: 4, bf16: 2), then with HASE
+  // the V1U = 4 e rows -- NT = 8 (fp32), 6 (bf16), or 4 / 2 without e. Nothing is stored inside the loop, so vmcnt
+  // counts loads only: once tile i's loads are issued, the operations issued after them are the loads of tiles
+  // i + 1 .. min(i + PF, V1CT - 1), k tiles of NT each, and tile i has landed at vmcnt(k NT) (at most 3 x 8 = 24 of
+  // the counter's 63).
+  __shared__ uint32_t red[V1CT][V1T / 64];
+  const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
+  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile_resid starts empty
+  const bool wide_ok = F.vec && v1_aligned16(F.data) && (!HASE || v1_aligned16(e_in));
+  constexpr int NX = V1Raw<DT_X>::N;                                  // 16-byte x loads per lane per tile
+  constexpr uint32_t TBX = V1TILE * (DT_X == DT_BF16 ? 8u : 16u);     // x bytes per tile
+  constexpr uint32_t TBE = V1TILE * 16u;                              // e bytes per tile
+  uint32_t packed[V1CT];
+  if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
+    const v1_v4i rsx = v1_rsrc((const char*)F.data + (size_t)t0 * TBX, V1CT * TBX);
+    const v1_v4i rse = v1_rsrc((const char*)e_in + (size_t)t0 * TBE, HASE ? V1CT * TBE : 0u);
+    constexpr uint32_t PF = V1_RESID_PF, RING = PF + 1;
+    v1_u4 bx[RING][NX], be[HASE ? RING : 1][V1U];
+    auto request = [&](uint32_t i) {
+#pragma unroll
+      for (int h = 0; h < NX; h++) bx[i % RING][h] = v1_ld16(i * TBX + (tid * NX + h) * 16u, rsx);
+      if constexpr (HASE) {
+#pragma unroll
+        for (uint32_t h = 0; h < V1U; h++) be[i % RING][h] = v1_ld16(i * TBE + (tid * V1U + h) * 16u, rse);
+      }
+    };
+#pragma unroll
+    for (uint32_t i = 0; i < PF && i < V1CT; i++) request(i);
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      if (i + PF < V1CT) request(i + PF);
+      v1_wait_tiles_xe<NX, HASE>(bx[i % RING], be[HASE ? i % RING : 0], (i + PF < V1CT ? PF : V1CT - 1 - i));
+      V1Raw<DT_X> rx;
+      V1Raw<DT_F32> re, y;
+#pragma unroll
+      for (int h = 0; h < NX; h++) {
+        const v1_u4 v = bx[i % RING][h];
+        rx.w[h] = make_uint4(v.x, v.y, v.z, v.w);
+      }
+#pragma unroll
+      for (uint32_t h = 0; h < V1U; h++) {
+        if constexpr (HASE) {
+          const v1_u4 v = be[i % RING][h];
+          re.w[h] = make_uint4(v.x, v.y, v.z, v.w);
+        } else {
+          re.w[h] = make_uint4(0u, 0u, 0u, 0u);
+        }
+      }
+      v1_form_y<DT_X>(rx, re, y);
+      uint32_t lsum;
+      packed[i] = v1_count_tile<DT_F32, true>(F, p, y, t0 + i, lsum);
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  } else {  // partial tiles, the padded last block, n % 4 != 0
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      uint32_t lsum = 0;
+      packed[i] = 0;
+      if (t0 + i < ntiles) {
+        V1Raw<DT_F32> y;
+        v1_load_y<DT_X>(F, HASE ? e_in : nullptr, t0 + i, y);
+        packed[i] = v1_count_tile<DT_F32>(F, p, y, t0 + i, lsum);
+      }
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < V1CT; i++)
+    if (t0 + i < ntiles) lens8[(size_t)(t0 + i) * V1T + tid] = packed[i];
+  __syncthreads();
+  if (tid < 64) {  // wave 0: the tile totals, and their sum for the scan's group totals
+    uint64_t tot = 0;
+    if (tid < V1CT && t0 + tid < ntiles) {
+#pragma unroll
+      for (uint32_t w = 0; w < V1T / 64; w++) tot += red[tid][w];
+      sums[t0 + tid] = tot;
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)tot, o, 64), hi = __shfl_xor((uint32_t)(tot >> 32), o, 64);
+      tot += (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    if (tid == 0) gsums[blockIdx.x] = tot;
+  }
+}
+
+// The e' rows of one tile: whole rows go through a buffer whose range is the tile's whole blocks inside the field (a
+// row past it is dropped: padding blocks give no residual, nothing lands past e_out[n - 1]); the real values of the
+// partial last block are stored one by one. The wide store is the compiler's builtin, not inline asm (DESIGN.md 5.1:
+// an inline-asm wide store after VALU writes stored stale lanes); aux 2 = non-temporal.
+struct V1ResidOut {
+  __amdgpu_buffer_rsrc_t rows;
+  float* e_out;
+  uint64_t nvals, b0;  // b0: the tile's first block
+  __device__ __forceinline__ V1ResidOut(float* e, uint64_t n, uint32_t t) : e_out(e), nvals(n), b0((uint64_t)t * V1TILE)
+  {
+    const uint64_t nfull = n / 4;
+    const uint32_t nrows = (uint32_t)min<uint64_t>(V1TILE, nfull > b0 ? nfull - b0 : 0ull);
+    rows = __builtin_amdgcn_make_buffer_rsrc(e + 4 * b0, 0, (int)(nrows * 16u), 0x00020000);
+  }
+  // row r of the tile
+  __device__ __forceinline__ void store_row(uint32_t r, v1_u4 v) const
+  {
+    __builtin_amdgcn_raw_buffer_store_b128(v, rows, (int)(r * 16u), 0, 2);
+    const uint32_t nv = (uint32_t)(nvals & 3u);
+    if (nv && b0 + r == nvals / 4) {
+      float* dst = e_out + 4 * (b0 + r);
+      dst[0] = __uint_as_float(v.x);
+      if (nv > 1) dst[1] = __uint_as_float(v.y);
+      if (nv > 2) dst[2] = __uint_as_float(v.z);
+    }
+  }
+  static __device__ __forceinline__ v1_u4 resid(const float* y, const float* d)
+  {
+    v1_u4 v;
+    v.x = resid_bits(y[0], d[0]);
+    v.y = resid_bits(y[1], d[1]);
+    v.z = resid_bits(y[2], d[2]);
+    v.w = resid_bits(y[3], d[3]);
+    return v;
+  }
+  // The lane's V1U rows after a 4 x 4 transpose inside its quad of lanes (two DPP quad_perm exchanges per register):
+  // store j of lane l then holds lane j's row l, so the quad's 16 rows leave as four contiguous 64-byte runs. Stored
+  // straight from the lane -- each store 16-byte pieces 64 bytes apart -- the whole call took 1.67 against 1.19 ms
+  // (fp32, accuracy 1e-3, 256 Mi values; profiles/r08_ef_var_time.log). Every lane of the quad must be active.
+  __device__ __forceinline__ void store_quad(v1_u4 (&r)[V1U]) const
+  {
+    static_assert(V1U == 4, "a 4 x 4 transpose");
+    const uint32_t l = threadIdx.x & 3u;
+#pragma unroll
+    for (int stage = 0; stage < 2; stage++) {
+      const bool hi = stage == 0 ? (l & 1u) != 0 : (l & 2u) != 0;
+#pragma unroll
+      for (int pr = 0; pr < 2; pr++) {
+        const int k0 = stage == 0 ? 2 * pr : pr, k1 = stage == 0 ? 2 * pr + 1 : pr + 2;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const uint32_t a = r[k0][c], b = r[k1][c];
+          const int send = (int)(hi ? a : b);
+          const uint32_t recv =
+              (uint32_t)(stage == 0 ? __builtin_amdgcn_mov_dpp(send, 0xB1, 0xf, 0xf, false)    // quad_perm [1, 0, 3, 2]
+                                    : __builtin_amdgcn_mov_dpp(send, 0x4E, 0xf, 0xf, false));  // quad_perm [2, 3, 0, 1]
+          r[k0][c] = hi ? recv : a;
+          r[k1][c] = hi ? b : recv;
+        }
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < V1U; j++) store_row((threadIdx.x & ~3u) * V1U + 4u * j + l, r[j]);
+  }
+};
+
+// v1_tile_code's hook: the block's residual row from the coefficients the coder was given, kept in the lane until the
+// tile is coded. Blocks with Inf / NaN (infmask) are redone by v1_tile_resid.
+struct V1ResidHook {
+  uint32_t& infmask;
+  v1_u4 (&rows)[V1U];
+  __device__ __forceinline__ void operator()(uint32_t k, const float* y, const uint32_t* u, uint32_t hdr, uint32_t K,
+                                             bool inf) const
+  {
+    infmask |= (uint32_t)inf << k;
+    float d[4];
+    v1_decode_closed(u, hdr, K, d);
+    rows[k] = V1ResidOut::resid(y, d);
+  }
+};
+
+// Code and store one tile of y and its residual.
+__device__ __forceinline__ void v1_tile_resid(const FieldDesc& F, const Params& p, float* e_out, uint32_t t, uint64_t B,
+                                              uint32_t total, const V1Raw<DT_F32>& y, uint32_t lw,
+                                              uint32_t* __restrict__ out32, uint64_t* __restrict__ index,
+                                              uint32_t index_shift, uint32_t ntiles, const uint32_t* tab,
+                                              const uint32_t* rs, uint64_t* win, uint32_t* scan_sh,
+                                              uint32_t* s_special)
+{
+  const V1ResidOut eo(e_out, F.n[0], t);
+  uint32_t infmask = 0;
+  v1_u4 rows[V1U];
+  v1_tile_code<DT_F32>(F, p, t, B, y, lw, index, index_shift, tab, rs, win, scan_sh, s_special,
+                       V1ResidHook{infmask, rows});
+  v1_tile_store(t, B, total, win, out32, ntiles);
+  if (infmask) {  // Inf / NaN present: the generic coder and decoder in the lane (padding blocks' rows are dropped)
+#pragma unroll
+    for (uint32_t k = 0; k < V1U; k++) {
+      if ((infmask >> k) & 1u) {
+        float f[4], d[4];
+        y.block(k, f);
+        (void)rt_block_generic(f, p, d);
+        rows[k] = V1ResidOut::resid(f, d);
+      }
+    }
+  }
+  eo.store_quad(rows);
+}
+
+template <int DT_X>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_resid(FieldDesc F, Params p, const float* e_in, float* e_out,
+                                                                 const uint64_t* __restrict__ rbase,
+                                                                 const uint32_t* __restrict__ lens8,
+                                                                 uint32_t* __restrict__ out32,
+                                                                 uint64_t* __restrict__ index, uint32_t index_shift,
+                                                                 uint32_t ntiles, uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t t = blockIdx.x;
+  // as in k_encode1d_var_tile, every load the tile needs is issued before anything waits: the x and e rows (all of
+  // the lane's e rows, before any e' store), the byte lengths, the pair table, the stream offsets
+  V1Raw<DT_F32> y;
+  v1_load_y<DT_X>(F, e_in, t, y);
+  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  const uint64_t B = rbase[t];
+  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel, nothing stored here
+    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
+    return;
+  }
+  v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
+}
+
+template <int DT_X>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid(FieldDesc F, Params p, const float* e_in,
+                                                                     float* e_out, const uint64_t* __restrict__ rbase,
+                                                                     const uint32_t* __restrict__ lens8,
+                                                                     uint32_t* __restrict__ out32,
+                                                                     uint64_t* __restrict__ index,
+                                                                     uint32_t index_shift, uint32_t ntiles,
+                                                                     const uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t n = over[0];
+  if (blockIdx.x >= n) return;
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t t = over[1 + i];
+    const uint64_t B = rbase[t];
+    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+    V1Raw<DT_F32> y;
+    v1_load_y<DT_X>(F, e_in, t, y);
+    const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+    v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh,
+                  &s_special);
+    __syncthreads();  // the window and scan slots are reused by the next tile
+  }
+}
+
+template <int DT_X>
+static hipError_t launch_resid1d_var_t(const FieldDesc& F, const Params& p, const float* e_in, float* e_out,
+                                       uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                       uint32_t index_shift, hipStream_t st)
+{
+  // the tile form's workspace layout (launch_encode1d_var_tile)
+  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
+  uint64_t* sums = ws;
+  uint64_t* base = ws + ntiles;
+  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
+  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
+  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
+  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
+  if (e_in) k_count1d_var_tile_resid<DT_X, true><<<ncw, V1T, 0, st>>>(F, p, e_in, ntiles, sums, lens8, over, gsums);
+  else k_count1d_var_tile_resid<DT_X, false><<<ncw, V1T, 0, st>>>(F, p, nullptr, ntiles, sums, lens8, over, gsums);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
+  if (e != hipSuccess) return e;
+  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
+  k_encode1d_var_tile_resid<DT_X><<<ntiles, V1T, 0, st>>>(F, p, e_in, e_out, base, lens8, out32, index, index_shift,
+                                                          ntiles, over);
+  k_encode1d_var_tile_big_resid<DT_X><<<nbig, V1T, 0, st>>>(F, p, e_in, e_out, base, lens8, out32, index, index_shift,
+                                                            ntiles, over);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_resid1d_var(const void* x, int x_dtype, uint64_t nvals, const Params& p, const float* e_in,
+                                     float* e_out, uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                     uint32_t index_shift, void* stream)
+{
+  FieldDesc F = {};
+  F.data = x;
+  F.n[0] = nvals;
+  F.n[1] = F.n[2] = F.n[3] = 1;
+  F.s[0] = 1;
+  F.nblocks = F.bx = (uint32_t)((nvals + 3) / 4);
+  F.by = F.bz = F.bw = 1;
+  F.dims = 1;
+  F.dtype = (uint32_t)x_dtype;
+  F.vec = ((uintptr_t)x % (x_dtype == DT_BF16 ? 8u : 16u)) == 0 ? 1u : 0u;
+  if (x_dtype == DT_BF16)
+    return launch_resid1d_var_t<DT_BF16>(F, p, e_in, e_out, out32, ws, d_total, index, index_shift,
+                                         (hipStream_t)stream);
+  return launch_resid1d_var_t<DT_F32>(F, p, e_in, e_out, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
 }
 
 }  // namespace gcow

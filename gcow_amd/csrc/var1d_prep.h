@@ -1,6 +1,7 @@
 // var1d_prep.h -- one 1-D block's coefficients, precision and bit length in closed form, for parameter sets whose
-// budget never truncates a block (minbits <= 1, maxbits >= 160): shared by the variable-rate encoder (var1d.hip) and
-// the fused round trip (roundtrip1d.hip).
+// budget never truncates a block (minbits <= 1, maxbits >= 160), and the block's decode from those coefficients without
+// a stream: shared by the variable-rate encoder and its residual form (var1d.hip), the fused round trip
+// (roundtrip1d.hip) and the fixed-rate residual encoder (enc_resid1d.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 
 #include "codec_device.h"
 #include "lean1d.h"
+#include "regbits.h"
 
 namespace gcow {
 
@@ -67,6 +69,42 @@ __device__ __forceinline__ uint32_t v1_prep(const float* f, int cexp, int maxpre
   const uint32_t e0 = (shl_hw(u[0], c0) >> 31) & min(K1 - c0, 1u);
   const uint32_t len = 4u + 4u * K - (c0 + c1 + c2) + (e0 + e1 + e2);
   return one ? 1u : 9u + len;
+}
+
+// The decode of a block no budget truncated, from v1_prep's u, hdr and K (K = 31 - kmin): an untruncated code holds
+// planes 31 .. kmin of every coefficient whole, so the decoder's coefficients are u_j with the planes below kmin
+// cleared; a block whose header is the single '0' bit (hdr = 0: a zero block, or no precision) decodes to +0. Then the
+// inverse negabinary map, inv_lift and dequant_scale(emax) * (float)q as decode_block has it (scale first, one
+// multiply: a subnormal maximum decodes to +-0). Not for blocks with Inf / NaN (v1_prep's inf): rt_block_generic.
+__device__ __forceinline__ void v1_decode_closed(const uint32_t* u, uint32_t hdr, uint32_t K, float* d)
+{
+  const uint32_t keep = hdr ? ~((1u << (31u - K)) - 1u) : 0u;
+  int32_t q[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) q[i] = (int32_t)(((u[i] & keep) ^ 0xaaaaaaaau) - 0xaaaaaaaau);
+  inv_lift(q[0], q[1], q[2], q[3]);
+  const float sc = dequant_scale((int)(hdr >> 1) - 127);  // hdr = 2 (emax + 127) + 1; hdr = 0: q = 0, any finite scale
+#pragma unroll
+  for (int i = 0; i < 4; i++) d[i] = sc * (float)q[i];
+}
+
+// Any parameter set: the block's code in three registers, decoded from them. Returns the block's bit length
+// (encode_block's return value: minbits padding and the maxbits cut included).
+__device__ __forceinline__ uint32_t rt_block_generic(const float* f, const Params& p, float* d)
+{
+  RegWriter192 wr{0ull, 0ull, 0ull, 0u};
+  const uint32_t len = encode_block<1>(wr, f, p);
+  RegReader192 rd{wr.w0, wr.w1, wr.w2};
+  decode_block<1>(rd, p, d);
+  return len;
+}
+
+// y - d as one IEEE subtract (no contraction, denormals kept); a non-finite result (NaN / Inf gradient, x + e overflow)
+// carries nothing forward
+__device__ __forceinline__ uint32_t resid_bits(float y, float d)
+{
+  const uint32_t r = __float_as_uint(__fsub_rn(y, d));
+  return (r & 0x7f800000u) == 0x7f800000u ? 0u : r;
 }
 
 }  // namespace gcow

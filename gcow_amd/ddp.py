@@ -19,7 +19,8 @@ device codec (gcow_amd.dist.DeviceCodec); tests inject an oracle-backed codec to
 
 Error feedback (`GcowHookState.error_feedback`, both wire hooks): what the codec truncates from a rank's bucket is
 kept on that rank and added to its next step's bucket before encoding, so the sent gradients average over steps to
-the meant ones (one fused kernel at rate 8 / 16: codec.encode_residual).
+the meant ones (codec.encode_residual: one fused kernel at rate 8 / 16, and the variable-rate encoder writing the
+residual from its own coefficients for accuracy / precision sets, which have no bit budget).
 """
 import contextlib
 import queue

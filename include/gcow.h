@@ -248,17 +248,34 @@ gcow_status gcow_encode_device_append(const zfp_input* field, const gcow_params*
  *      Inf gradient (an AMP overflow step) or an overflowing x + e does not stay in the carried error.
  * The padding values of a partial last block give no residual: nothing is written past e_out[n - 1], nor past the
  * stream's flushed words. Over steps the sent values then average to the meant ones: sum_t yhat_t = sum_t x_t + e_0 - e_T.
- * Fixed rate with whole-word blocks (minbits == maxbits in {32, 64}, maxprec >= 32, minexp <= -154; rate 8 and 16),
- * 16-byte aligned rows and no d_index: one fused kernel (each block coded, its word decoded in registers, both outputs
- * stored: 14 bytes of HBM traffic per fp32 value at rate 16), no workspace. Every other 1-D parameter set (and a lean
- * call with d_index, or with buffers off 16-byte alignment) is composed from the existing kernels: y into the
- * workspace, the encoders on y, the decoder into d_err_out, r in place; a variable-rate stream is decoded through the
- * caller's block index, or (d_index NULL) through one every 16 blocks kept in the workspace.
- * gcow_encode_residual_workspace_bytes covers y, the encoder's workspace and that index (0 for the fused kernel;
- * decided from p and, when field->data is set, its alignment). Capacity and workspace checks as gcow_encode_device.
- * Asynchronous on hip_stream; no host synchronisation, no allocation.
+ * Three paths give that result (gcow_encode_residual_path tells which one a call takes):
+ *   GCOW_RESID_FUSED_FIXED  fixed rate with whole-word blocks (minbits == maxbits in {32, 64}, maxprec >= 32,
+ *      minexp <= -154; rate 8 and 16), 16-byte aligned rows and no d_index: one kernel (each block coded, its word
+ *      decoded in registers, both outputs stored: 14 bytes of HBM traffic per fp32 value at rate 16). No workspace.
+ *   GCOW_RESID_FUSED_VAR    parameter sets whose budget truncates no block (minbits <= 1, maxbits >= 160: accuracy,
+ *      precision, expert sets of that shape), field->data, d_err_in and d_err_out 16-byte aligned, with or without
+ *      d_index at any legal stride: the variable-rate encoder's count, scan and code passes run on y formed in
+ *      registers, and the code pass writes e_out from the coefficients it codes -- in this domain the decode of a
+ *      block is those coefficients with the planes below kmin cleared, so no decoder runs, the stream is not read
+ *      back and no index is needed. The workspace is gcow_encode_workspace_bytes of the fp32 field of n values.
+ *   GCOW_RESID_COMPOSED     every other 1-D call (a budgeted variable-rate set, any other fixed rate, a lean call with
+ *      d_index, buffers off 16-byte alignment): y into the workspace, the encoders on y, the decoder into d_err_out,
+ *      r in place; a variable-rate stream is decoded through the caller's block index, or (d_index NULL) through one
+ *      every 16 blocks kept in the workspace. The workspace covers y, the encoder's workspace and that index.
+ * gcow_encode_residual_workspace_bytes is decided from p and, when field->data is set, its alignment (the error
+ * buffers are taken as aligned; a call whose buffers turn out otherwise needs the composed path's size, which the
+ * function returns for a field whose data pointer is set and off alignment). Capacity and workspace checks as
+ * gcow_encode_device. Asynchronous on hip_stream; no host synchronisation, no allocation.
  * GCOW_ERR_UNSUPPORTED: dims != 1, a non-unit stride, a dtype other than float / bf16. GCOW_ERR_INVALID: NULL d_err_out.
+ *
+ * gcow_encode_residual_path: the path gcow_encode_residual_device takes for these arguments, or -1 for a call it
+ * refuses. The pointers are inspected for alignment only and never dereferenced; NULL field->data or d_err_out means
+ * "assume aligned" (d_err_in NULL is aligned: there is no input error). All three functions decide through the same
+ * rule.
  */
+enum { GCOW_RESID_COMPOSED = 0, GCOW_RESID_FUSED_FIXED = 1, GCOW_RESID_FUSED_VAR = 2 };
+int gcow_encode_residual_path(const zfp_input* field, const gcow_params* p, const float* d_err_in,
+                              const float* d_err_out, const uint64_t* d_index);
 size_t gcow_encode_residual_workspace_bytes(const zfp_input* field, const gcow_params* p);
 gcow_status gcow_encode_residual_device(const zfp_input* field, const gcow_params* p, const float* d_err_in,
                                         float* d_err_out, void* d_out, size_t out_capacity, uint64_t* d_total_bits,
