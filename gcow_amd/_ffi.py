@@ -111,6 +111,10 @@ def load():
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),
         "gcow_decode_mean_device": (i32, [pi, pp, vp, sz, u64, u32, vp, u64, u32, vp]),
+        "gcow_decode_mean_encode_path": (i32, [pi, pp, pp, vp, vp, vp, vp]),
+        "gcow_decode_mean_encode_workspace_bytes": (sz, [pi, pp, pp]),
+        "gcow_decode_mean_encode_device": (i32, [pi, pp, vp, sz, u64, u32, vp, u64, u32, pp, vp, vp, vp, sz, vp, vp,
+                                                 sz, vp, u32, vp]),
         "gcow_index_pack16_device": (i32, [pi, pp, vp, vp, vp]),
         "gcow_header_bits": (C.c_uint, [pp]),
         "gcow_write_header": (C.c_uint, [pi, pp, P(u64)]),

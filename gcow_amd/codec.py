@@ -328,6 +328,88 @@ def decode_mean(streams: torch.Tensor, stream_words: int, nstreams: int, n: int,
     return out
 
 
+MEANENC_COMPOSED, MEANENC_FUSED_FIXED = 0, 1  # gcow_decode_mean_encode_path
+
+
+class ReduceEncoder:
+    """Preallocated decode + mean + encode (gcow_decode_mean_encode_device) for `nstreams` received streams of one 1-D
+    shard of n values under `params_in`: calling it codes their fp32 mean (decode_mean's values) under `params_out`
+    (default: params_in) without the mean travelling through memory where the call runs fused. `path`
+    (gcow_decode_mean_encode_path, for 16-byte aligned buffers): MEANENC_FUSED_FIXED when both sets are the same rate 8
+    / 16 set and no index goes in or out (one kernel, no workspace), else MEANENC_COMPOSED (decode_mean into an fp32
+    temporary in the workspace, then the encoder on it). residual=True: calls take `err` (fp32, n values, updated in
+    place): y = mean + err is coded and err = finite(y - decode(stream)), as ResidualEncoder does for a bucket. The
+    stream, bit count, output index and workspace are allocated once."""
+
+    def __init__(self, n: int, params_in: GcowParams, nstreams: int, params_out: GcowParams | None = None, device=None,
+                 residual: bool = False, index_stride_out: int = 0):
+        self.L = load()
+        self.n, self.nstreams = int(n), int(nstreams)
+        self.params_in = params_in
+        self.params = params_out if params_out is not None else params_in
+        self.device = torch.device(device or "cuda")
+        self.residual = bool(residual)
+        self.shape = (self.n,)
+        f = field_of_shape(self.shape, torch.float32)
+        pi, po = C.byref(self.params_in), C.byref(self.params)
+        self.cap = self.L.gcow_max_output_bytes(C.byref(f), po) if self.n else 8
+        if self.cap == 0:
+            raise GcowError("unsupported shard of %d values" % self.n)
+        self.words = torch.zeros((self.cap + 7) // 8, dtype=torch.int64, device=self.device)
+        self.bits_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.fixed = is_fixed(self.params)
+        if self.fixed:  # fixed rate: the bit count is known on the host; no device write per call
+            self.bits_dev.fill_((self.n + 3) // 4 * self.params.maxbits)
+        self.index_stride = index_stride_out
+        ne = self.L.gcow_index_entries(C.byref(f), index_stride_out) if index_stride_out and self.n else 0
+        self.index = torch.zeros(max(ne, 1), dtype=torch.int64, device=self.device) if index_stride_out else None
+        # the path for aligned buffers: pointers are looked at for presence only (1 = "an index is given")
+        self.path = self.L.gcow_decode_mean_encode_path(C.byref(f), pi, po, None, None,
+                                                        None if is_fixed(params_in) else 1,
+                                                        1 if index_stride_out else None) if self.n else MEANENC_COMPOSED
+        ws = self.L.gcow_decode_mean_encode_workspace_bytes(C.byref(f), pi, po)
+        if self.n and self.path == MEANENC_COMPOSED and ws == 0:
+            # the query decides from the parameter sets alone; an output index sends a rate 8 / 16 call to the
+            # composed path: the mean, then the larger of the two inner calls' workspaces
+            a256 = lambda v: (v + 255) // 256 * 256
+            ws = a256(4 * self.n) + max(a256(self.L.gcow_encode_workspace_bytes(C.byref(f), po)),
+                                        self.L.gcow_encode_residual_workspace_bytes(C.byref(f), po))
+        self.ws_bytes = ws
+        self.ws = torch.zeros(max(ws // 8, 1), dtype=torch.int64, device=self.device)
+
+    def __call__(self, streams: torch.Tensor, stream_words: int, index: torch.Tensor | None = None,
+                 index_words: int = 0, index_stride: int = 0, err: torch.Tensor | None = None,
+                 stream=None) -> Encoded:
+        if not (streams.is_cuda and streams.dtype == torch.int64 and streams.is_contiguous()):
+            raise GcowError("ReduceEncoder expects a contiguous int64 device tensor of stream words")
+        if self.residual != (err is not None):
+            raise GcowError("ReduceEncoder(residual=%s) called %s err" % (self.residual,
+                                                                         "with" if err is not None else "without"))
+        if err is not None and not (err.is_cuda and err.device == streams.device and err.dtype == torch.float32
+                                    and err.is_contiguous() and err.numel() == self.n):
+            raise GcowError("ReduceEncoder: err must be a contiguous fp32 tensor of n values on the streams' device")
+        f = field_of_shape(self.shape, torch.float32)
+        ep = err.data_ptr() if err is not None and self.n else None
+        st = self.L.gcow_decode_mean_encode_device(
+            C.byref(f), C.byref(self.params_in), streams.data_ptr(), streams.numel() * 8, stream_words, self.nstreams,
+            index.data_ptr() if index is not None else None, index_words, index_stride,
+            C.byref(self.params), ep, ep, self.words.data_ptr(), self.cap,
+            None if self.fixed else self.bits_dev.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+            self.index.data_ptr() if self.index is not None else None, self.index_stride, _stream_ptr(stream))
+        check(st, "gcow_decode_mean_encode_device")
+        return Encoded(self.words, self.bits_dev, self.shape, self.params, self.index, self.index_stride)
+
+
+def decode_mean_encode(streams: torch.Tensor, stream_words: int, nstreams: int, n: int, params: GcowParams,
+                       index: torch.Tensor | None = None, index_words: int = 0, index_stride: int = 0,
+                       out_params: GcowParams | None = None, err: torch.Tensor | None = None,
+                       out_index_stride: int = 0, stream=None) -> Encoded:
+    """One-shot ReduceEncoder: the stream `encode` gives for decode_mean(streams, ...) under out_params (default:
+    params); with `err`, the stream of mean + err, and err updated in place as encode_residual does."""
+    enc = ReduceEncoder(n, params, nstreams, out_params, streams.device, err is not None, out_index_stride)
+    return enc(streams, stream_words, index, index_words, index_stride, err, stream)
+
+
 def pack_index16(index8: torch.Tensor, n: int, params: GcowParams, out: torch.Tensor | None = None,
                  stream=None) -> torch.Tensor:
     """The packed 16-block index (gcow_index_pack16_device) of one stream of n values from its index every 8 blocks:

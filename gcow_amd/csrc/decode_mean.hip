@@ -9,6 +9,7 @@
 #include "dec1d.h"
 #include "field_io.h"
 #include "kernels.h"
+#include "mean1d.h"
 #include "pipe.h"
 
 // ---- tunables (A/B builds: tools/build_variant.sh)
@@ -28,24 +29,6 @@
 namespace gcow {
 
 // ------------------------------------------------------------------------------------------------ decode + mean
-// acc / nstreams for the N sums of a lane: an IEEE division, or -- nstreams a power of two (the usual world size) --
-// the product by the exact reciprocal, which is the same correctly rounded value of the same quotient (a uniform
-// branch: the division's expansion runs only for other world sizes).
-template <int N>
-__device__ __forceinline__ void mean_scale(float* a, uint32_t nstreams)
-{
-#pragma clang fp contract(off)
-  if ((nstreams & (nstreams - 1u)) == 0u) {
-    const float inv = 1.0f / (float)nstreams;
-#pragma unroll
-    for (int i = 0; i < N; i++) a[i] = a[i] * inv;
-  } else {
-    const float nf = (float)nstreams;
-#pragma unroll
-    for (int i = 0; i < N; i++) a[i] = a[i] / nf;
-  }
-}
-
 // The receive side of the compressed all-gather hook: nstreams 1-D streams of the same shape
 // (one per rank, stream_words apart) are decoded and averaged in one launch instead of one decode and one add per
 // rank. Each lane accumulates in fp32 in rank order, acc = ((0 + x_0) + x_1) + ..., then stores acc / nstreams: the
@@ -89,23 +72,6 @@ __global__ __launch_bounds__(256) void k_decode_mean_fixed1d(FieldDesc F, Params
 // the stream loop, and a value loaded by inline asm must not be carried (the loop's register copies would read the
 // destination before the load has written it). Full blocks only (the launcher sends a partial last block to
 // k_decode_mean_fixed1d).
-template <uint32_t WB> struct MeanWord;
-template <> struct MeanWord<64> {
-  typedef uint64_t T;
-  static __device__ __forceinline__ T load(__amdgpu_buffer_rsrc_t rs, uint32_t b)
-  {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(b * 8u), 0, 0);
-    return (uint64_t)v[0] | ((uint64_t)v[1] << 32);
-  }
-};
-template <> struct MeanWord<32> {
-  typedef uint32_t T;
-  static __device__ __forceinline__ T load(__amdgpu_buffer_rsrc_t rs, uint32_t b)
-  {
-    return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(b * 4u), 0, 0);
-  }
-};
-
 template <uint32_t WB, int U, int D>
 __global__ __launch_bounds__(256) void k_decode_mean_fixed1d_np(FieldDesc F, Params p, const uint64_t* __restrict__ in,
                                                                 uint64_t stream_words, uint32_t nstreams,

@@ -1172,6 +1172,137 @@ gcow_status gcow_decode_mean_device(const zfp_input* field, const gcow_params* p
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- decode + mean + encode
+// 1-D, n values; fills the fp32 field of the mean (data unset)
+static gcow_status meanenc_field(const zfp_input* field, zfp_input& mf)
+{
+  if (!field) return fail(GCOW_ERR_INVALID, "null field");
+  if (field->ny || field->nz || field->nw) return fail(GCOW_ERR_UNSUPPORTED, "decode_mean_encode takes 1-D fields");
+  std::memset(&mf, 0, sizeof(mf));
+  mf.dtype = dtype_float;
+  mf.nx = field->nx;
+  return GCOW_OK;
+}
+
+static bool same_params(const gcow_params& a, const gcow_params& b)
+{
+  return a.minbits == b.minbits && a.maxbits == b.maxbits && a.maxprec == b.maxprec && a.minexp == b.minexp;
+}
+
+// The one rule behind gcow_decode_mean_encode_path, _workspace_bytes and _device: -1 = refused, else GCOW_MEANENC_*.
+// Pointers are looked at for presence (the indexes) and alignment (the error buffers; NULL: aligned) only.
+static int meanenc_path(const zfp_input* field, const gcow_params* p_in, const gcow_params* p_out,
+                        const float* d_err_in, const float* d_err_out, const uint64_t* d_index_in,
+                        const uint64_t* d_index_out)
+{
+  zfp_input mf;
+  if (meanenc_field(field, mf) || check_params(p_in, 1) || check_params(p_out, 1)) return -1;
+  if ((uint64_t)(mf.nx + 3) / 4 >= (1ull << 32)) {
+    fail(GCOW_ERR_UNSUPPORTED, "more than 2^32 blocks per call");
+    return -1;
+  }
+  const uintptr_t e = (uintptr_t)d_err_in | (uintptr_t)d_err_out;
+  if (e % 4) {
+    fail(GCOW_ERR_INVALID, "misaligned error buffer");
+    return -1;
+  }
+  if (d_err_in && !d_err_out) {
+    fail(GCOW_ERR_INVALID, "d_err_in without d_err_out");
+    return -1;
+  }
+  if (same_params(*p_in, *p_out) && resid_lean_params(*p_in) && !d_index_in && !d_index_out && e % 16 == 0)
+    return GCOW_MEANENC_FUSED_FIXED;
+  return GCOW_MEANENC_COMPOSED;
+}
+
+int gcow_decode_mean_encode_path(const zfp_input* field, const gcow_params* p_in, const gcow_params* p_out,
+                                 const float* d_err_in, const float* d_err_out, const uint64_t* d_index_in,
+                                 const uint64_t* d_index_out)
+{
+  return meanenc_path(field, p_in, p_out, d_err_in, d_err_out, d_index_in, d_index_out);
+}
+
+// composed path: the mean's n fp32 values at the head, the inner call's workspace behind (the query does not know
+// whether the call carries error buffers: room for either inner call)
+static size_t meanenc_inner_ws(const zfp_input& mf, const gcow_params* p_out)
+{
+  return std::max(align256(gcow_encode_workspace_bytes(&mf, p_out)), gcow_encode_residual_workspace_bytes(&mf, p_out));
+}
+
+size_t gcow_decode_mean_encode_workspace_bytes(const zfp_input* field, const gcow_params* p_in,
+                                               const gcow_params* p_out)
+{
+  zfp_input mf;
+  if (!p_in || !p_out || meanenc_field(field, mf) || !mf.nx) return 0;
+  const int path = meanenc_path(field, p_in, p_out, nullptr, nullptr, nullptr, nullptr);
+  if (path < 0 || path == GCOW_MEANENC_FUSED_FIXED) return 0;
+  return align256((size_t)mf.nx * 4) + meanenc_inner_ws(mf, p_out);
+}
+
+gcow_status gcow_decode_mean_encode_device(const zfp_input* field, const gcow_params* p_in, const uint64_t* d_streams,
+                                           size_t streams_bytes, uint64_t stream_words, uint32_t nstreams,
+                                           const uint64_t* d_index_in, uint64_t index_words, uint32_t index_stride_in,
+                                           const gcow_params* p_out, const float* d_err_in, float* d_err_out,
+                                           void* d_out, size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                           size_t workspace_bytes, uint64_t* d_index_out, uint32_t index_stride_out,
+                                           void* hip_stream)
+{
+  zfp_input mf;
+  gcow_status st = meanenc_field(field, mf);
+  if (st) return st;
+  if ((st = check_params(p_in, 1)) || (st = check_params(p_out, 1))) return st;
+  if (d_err_in && !d_err_out) return fail(GCOW_ERR_INVALID, "d_err_in without d_err_out");
+  if (((uintptr_t)d_err_in | (uintptr_t)d_err_out) % 4) return fail(GCOW_ERR_INVALID, "misaligned error buffer");
+  if (mf.nx == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  const int path = meanenc_path(field, p_in, p_out, d_err_in, d_err_out, d_index_in, d_index_out);
+  if (path < 0) return GCOW_ERR_UNSUPPORTED;  // more than 2^32 blocks: every other refusal was returned above
+  // the mean's field: the workspace head on the composed path; the fused kernel never forms it, so any aligned
+  // non-null address serves the argument checks below
+  const size_t mbytes = align256((size_t)mf.nx * 4);
+  if (path == GCOW_MEANENC_COMPOSED) {
+    if (!d_workspace || workspace_bytes < mbytes + meanenc_inner_ws(mf, p_out) || (uintptr_t)d_workspace % 16)
+      return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_decode_mean_encode_workspace_bytes() (error buffers "
+                                    "off 16-byte alignment and calls with an index take the composed path at every "
+                                    "parameter set), or not 16-byte aligned");
+    mf.data = d_workspace;
+  }
+  // the checks of the two calls this one is defined by, before anything is launched
+  if (!nstreams || !d_streams) return fail(GCOW_ERR_INVALID, "no streams");
+  if (streams_bytes / 8 < (uint64_t)nstreams * stream_words + 2)
+    return fail(GCOW_ERR_INVALID, "stream buffer smaller than nstreams * stream_words + 2 words");
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if (out_capacity < gcow_max_output_bytes(&mf, p_out))
+    return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_max_output_bytes()");
+  if (d_index_out && (!index_stride_out || index_stride_out > 256 || (index_stride_out & (index_stride_out - 1))))
+    return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+  if (path == GCOW_MEANENC_FUSED_FIXED) {
+    const uint64_t nb = ((uint64_t)mf.nx + 3) / 4;
+    if (index_stride_in || index_words)
+      return fail(GCOW_ERR_INVALID, "fixed-rate decode_mean takes no block index (blocks are at b * maxbits)");
+    if (stream_words < (nb * p_in->maxbits + 63) / 64)
+      return fail(GCOW_ERR_INVALID, "stream_words below one fixed-rate stream");
+    GCOW_HIP(gcow::launch_decode_mean_encode_fixed1d(mf.nx, P(*p_in), d_streams, stream_words, nstreams, d_err_in,
+                                                     d_err_out, d_out, hip_stream));
+    if (p_out->maxbits == 32 && (nb & 1))  // stream_flush: zero the upper half of the last word
+      GCOW_HIP(hipMemsetAsync((uint32_t*)d_out + nb, 0, 4, (hipStream_t)hip_stream));
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, nb * p_out->maxbits, hip_stream));
+    return GCOW_OK;
+  }
+  if ((st = gcow_decode_mean_device(&mf, p_in, d_streams, streams_bytes, stream_words, nstreams, d_index_in,
+                                    index_words, index_stride_in, hip_stream)))
+    return st;
+  void* inner = (char*)d_workspace + mbytes;
+  const size_t inner_bytes = workspace_bytes - mbytes;
+  if (d_err_out)
+    return gcow_encode_residual_device(&mf, p_out, d_err_in, d_err_out, d_out, out_capacity, d_total_bits, inner,
+                                       inner_bytes, d_index_out, index_stride_out, hip_stream);
+  return encode_impl(&mf, p_out, d_out, out_capacity, d_total_bits, inner, inner_bytes, d_index_out, index_stride_out,
+                     hip_stream);
+}
+
 gcow_status gcow_index_pack16_device(const zfp_input* field, const gcow_params* p, const uint64_t* d_index8,
                                      uint64_t* d_out, void* hip_stream)
 {

@@ -126,6 +126,12 @@ hipError_t launch_index_pack16(const uint64_t* idx8, uint64_t n8, uint64_t* out,
 hipError_t launch_decode_mean1d(const FieldDesc& F, const Params& p, const uint64_t* in, uint64_t stream_words,
                                 uint32_t nstreams, const uint64_t* index, uint64_t index_words, void* stream,
                                 uint32_t chunk = 16);  // chunk: variable rate's index stride, 8 or 16, or kIndexPacked16
+// W stream pieces straight into the stream of their mean (mean_enc1d.hip): the lean fixed-rate domain, no index; the
+// values gcow_decode_mean_device gives are coded as launch_encode_fixed1d codes them (e_out null) or, with e_out, as
+// launch_encode_resid1d codes them with e_in (null: zeros; e_in == e_out allowed; 16-byte aligned rows)
+hipError_t launch_decode_mean_encode_fixed1d(uint64_t nvals, const Params& p, const uint64_t* in,
+                                             uint64_t stream_words, uint32_t nstreams, const float* e_in, float* e_out,
+                                             void* out, void* stream);
 hipError_t launch_stage(int which, int dims, const void* a, const void* b, uint32_t n, void* out, uint32_t x0,
                         uint32_t x1, void* out2, uint32_t slot_words, void* stream);
 hipError_t launch_fill_normal(float* out, uint64_t count, double sigma, uint64_t seed, int inject, void* stream);

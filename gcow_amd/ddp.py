@@ -65,7 +65,17 @@ class GcowHookState:
     again. Buckets of equal size that the rebuild permutes are not told apart -- one step's error of the other bucket
     is then added once; `reset_error_feedback()` after the first iteration avoids it. roundtrip_hook raises ValueError
     with the flag set: its loss is applied after the reduction, identically on every rank. Unset (the default):
-    nothing changes and encode_residual is never called."""
+    nothing changes and encode_residual is never called.
+
+    `compress_mean` (compressed_sharded_hook only; the other two hooks raise ValueError with it set): the second stage
+    of the sharded exchange -- the all-gather of the mean shards -- carries streams instead of values. The owner of a
+    shard turns its W received pieces straight into the stream of their mean (codec.ReduceEncoder: one kernel at rate
+    8 / 16) under `mean_params` (None: `params`), the streams are all-gathered and every rank decodes every shard, the
+    owner its own too, so that all ranks hold decode(encode(mean)) bit for bit. With `error_feedback` the owner also
+    keeps a second carried error, of its mean shard (keyed by bucket index, "mean" and the shard's numel; cleared by
+    reset_error_feedback()). Per rank, n fp32 values at rate 16 then cost 7/8 (2n + 2n) bytes instead of
+    7/8 (2n + 4n) at W = 8. The mean is coded from its fp32 values whatever the bucket's dtype: for a bf16 bucket the
+    second stage saves bytes only below 16 bits per value. Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -75,6 +85,9 @@ class GcowHookState:
     sharded: bool = False
     # error feedback for the wire hooks (class docstring); roundtrip_hook refuses it
     error_feedback: bool = False
+    # compressed_sharded_hook: the mean shards travel compressed too (class docstring); the other hooks refuse it
+    compress_mean: bool = False
+    mean_params: GcowParams | None = None  # the mean's parameter set; None: `params`
     _worker: object = field(default=None, repr=False)
     _side: dict = field(default_factory=dict, repr=False)
     _comm_group: object = field(default=None, repr=False)
@@ -137,6 +150,17 @@ class GcowHookState:
             e = self._errors[index] = torch.zeros(x.numel(), dtype=torch.float32, device=x.device)
         return e
 
+    def mean_error_buffer(self, index, numel: int, device) -> torch.Tensor:
+        """compress_mean with error_feedback: the carried error of this rank's mean shard of bucket `index`, keyed by
+        (index, "mean", numel): fp32 zeros at first use; a shard whose size changed drops the buffer kept before."""
+        key = (index, "mean", numel)
+        e = self._errors.get(key)
+        if e is None or e.device != device:
+            for k in [k for k in self._errors if isinstance(k, tuple) and len(k) == 3 and k[:2] == key[:2]]:
+                del self._errors[k]
+            e = self._errors[key] = torch.zeros(numel, dtype=torch.float32, device=device)
+        return e
+
     def reset_error_feedback(self):
         """Forget every carried error (the next step starts from zeros): after loading a checkpoint, changing the
         codec parameters, or skipping a step whose gradients were discarded."""
@@ -191,6 +215,9 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
     if state.error_feedback:
         raise ValueError("error_feedback is for the wire hooks (compressed_allgather_hook, compressed_sharded_hook): "
                          "roundtrip_hook applies its loss after the reduction, identically on every rank")
+    if state.compress_mean:
+        raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
+                         "roundtrip_hook puts no mean shard on the wire")
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -270,6 +297,9 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     padded all-gather; that read and the collectives after it run on the state's comm thread (on a side stream that
     waits for the encode), and the returned future completes when the mean is written. Each bucket encodes into its
     own buffers (slot = bucket index), so a later bucket's encode never overwrites a stream still in flight."""
+    if state.compress_mean:
+        raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
+                         "compressed_allgather_hook decodes every rank's stream on every rank and sends no mean")
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -331,6 +361,29 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     return state.worker().submit(exchange, fut)
 
 
+def _mean_stream(state: GcowHookState, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev):
+    """compress_mean: the stream (words, bits, index) of the mean of this rank's `world` received pieces under
+    state.mean_params, with error feedback on the mean shard when the state asks for it; (None, None, None) for an
+    empty shard. Runs inside the exchange, on the side stream: the carried error and the cached encoder's buffers are
+    allocated there."""
+    if hi <= lo:
+        return None, None, None
+    p = state.params
+    mp = state.mean_params or p
+    ostride = 0 if _codec.is_fixed(mp) else gdist.MEAN_INDEX_STRIDE
+    err = None
+    if state.error_feedback:
+        err = state.mean_error_buffer(bidx, hi - lo, dev)
+    slot = ("sharded-mean", bidx)
+    if hasattr(cdc, "decode_mean_encode"):
+        return cdc.decode_mean_encode(pieces, pw, world, hi - lo, p, pidx, iw, stride, out_params=mp, err=err,
+                                      out_index_stride=ostride, slot=slot)
+    m = cdc.decode_mean(pieces, pw, world, hi - lo, p, pidx, iw, stride)  # an fp32 temporary
+    if err is not None:
+        return cdc.encode_residual(m, err, mp, ostride, slot=slot)
+    return cdc.encode(m, mp, ostride, slot=slot)
+
+
 def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
     """The compressed exchange with a sharded receive side (gcow_amd.dist "sharded receive"): each rank encodes its
     bucket, cuts its stream at the shard boundaries (fixed rate: at b * maxbits; variable rate: at the block index)
@@ -340,7 +393,11 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     compressed_allgather_hook's (the same fp32 sums in rank order); per rank it receives (W - 1) / W of one stream
     instead of W - 1 streams and decodes 1 / W of the values, for an extra all-gather of the mean. Collectives run on
     the state's comm thread over its exchange group (GcowHookState.setup, every rank), on a side stream that waits
-    for the encode; the returned future completes when the bucket holds the mean."""
+    for the encode; the returned future completes when the bucket holds the mean.
+
+    With state.compress_mean the second stage is compressed too (gcow_amd.dist.allgather_mean_streams): the owner
+    codes the mean of its pieces without storing it (cdc.decode_mean_encode; a codec without that method composes
+    decode_mean and encode), and the bucket ends as decode(encode(mean)) under state.mean_params on every rank."""
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -351,7 +408,8 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     fixed = _codec.is_fixed(p)
     stride = 0 if fixed else SHARDED_INDEX_STRIDE
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    slot = ("sharded", bucket.index() if hasattr(bucket, "index") else None)
+    bidx = bucket.index() if hasattr(bucket, "index") else None
+    slot = ("sharded", bidx)
     words, bits, index = _encode(state, cdc, bucket, x, stride, slot)
     dev = x.device
     if dev.type == "cuda":
@@ -380,6 +438,11 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
                 pieces, pw, pidx, iw, lo, hi = gdist.shard_pieces_variable(words, bits, index, n, stride, cgroup)
             direct = flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous()
             shard = flat[lo:hi] if direct else torch.empty(hi - lo, dtype=torch.float32, device=dev)
+            if state.compress_mean:
+                mwords, mbits, midx = _mean_stream(state, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev)
+                gdist.allgather_mean_streams(flat, mwords, mbits, midx, n, state.mean_params or p, cgroup, cdc)
+                fut.set_result(buf)
+                return
             if hi > lo:
                 cdc.decode_mean(pieces, pw, world, hi - lo, p, pidx, iw, stride, out=shard)
             gdist.allgather_shards(flat, shard if direct else shard.to(flat.dtype), n, cgroup)

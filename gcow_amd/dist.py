@@ -72,6 +72,28 @@ class DeviceCodec:
         self._evict_idle()
         return ent[0]
 
+    def decode_mean_encode(self, streams, stream_words: int, nstreams: int, n: int, params, index=None,
+                           index_words: int = 0, index_stride: int = 0, out_params=None, err=None,
+                           out_index_stride: int = 0, slot=None):
+        """The stream of the mean of nstreams received streams (codec.ReduceEncoder): -> (words, bits, index) as
+        `encode` of decode_mean(...) under out_params (default: params) returns them; with `err` (fp32, n values,
+        updated in place) as `encode_residual` of that mean. Cached per slot like the encoders."""
+        from . import codec
+        self._tick += 1
+        po = out_params if out_params is not None else params
+        key = (slot, n, nstreams, streams.device, params.tuple(), po.tuple(), out_index_stride, err is not None,
+               "reduce")
+        ent = self._enc.get(key)
+        if ent is None:
+            ent = self._enc[key] = [codec.ReduceEncoder(n, params, nstreams, po, streams.device, err is not None,
+                                                        out_index_stride), self._tick]
+        else:
+            ent[1] = self._tick
+            self._enc.move_to_end(key)
+        self._evict_idle()
+        e = ent[0](streams, stream_words, index, index_words, index_stride, err)
+        return e.words, e.bits_dev, e.index
+
     def _evict_idle(self):
         limit = self.idle_factor * len(self._enc) + self.idle_slack
         while self._enc:
@@ -286,8 +308,10 @@ def shard_pieces_variable(words: torch.Tensor, bits, index: torch.Tensor, nvals:
     bits_t = bits.reshape(1).to(device=dev, dtype=torch.int64) if isinstance(bits, torch.Tensor) else \
         torch.tensor([int(bits)], dtype=torch.int64, device=dev)
     cut = torch.empty(world + 1, dtype=torch.int64, device=dev)
-    for r, (lo, hi) in enumerate(bounds):  # an empty shard (lo = nvals) starts at the stream's end
-        if lo // 4 < nb:
+    # an empty shard (lo = hi = nvals) starts at the stream's end; nvals need not be a block multiple, so the test is
+    # on the shard, not on lo's block (a bucket with a partial last block and empty shards lost its last piece)
+    for r, (lo, hi) in enumerate(bounds):
+        if hi > lo:
             cut[r:r + 1] = index[starts[r]:starts[r] + 1]
         else:
             cut[r:r + 1] = bits_t
@@ -321,6 +345,69 @@ def shard_pieces_variable(words: torch.Tensor, bits, index: torch.Tensor, nvals:
     alltoall_into(pidx, isend, group)
     lo, hi = bounds[rank]
     return pieces, pw, pidx, iw, lo, hi
+
+
+MEAN_INDEX_STRIDE = 16  # block index spacing of a variable-rate mean shard's stream (allgather_mean_streams)
+
+
+def mean_stream_plan(nvals: int, world: int, maxbits: int):
+    """Fixed rate: the words every rank contributes to allgather_mean_streams -- a full shard's stream (a 64-block
+    multiple: whole words), or the whole bucket's flushed stream when it is shorter than one full shard."""
+    nb = (nvals + 3) // 4
+    per_b = ((nb + world - 1) // world + SHARD_ALIGN_BLOCKS - 1) // SHARD_ALIGN_BLOCKS * SHARD_ALIGN_BLOCKS
+    return (min(per_b, nb) * maxbits + 63) // 64
+
+
+def allgather_mean_streams(flat: torch.Tensor, words, bits, index, nvals: int, params, group=None, codec=None):
+    """The sharded exchange's second stage with the mean compressed: every rank contributes the stream of its mean
+    shard (`words`, `bits`, and at variable rate `index` every MEAN_INDEX_STRIDE blocks, as `encode` returns them for
+    the shard's values; ignored on a rank whose shard is empty), and `flat` (the bucket, n values, any dtype) receives
+    the decode of every shard's stream -- the owner's own included, so every rank ends with the same bits.
+    Fixed rate: each stream zero-padded to mean_stream_plan words, one all-gather; the gathered buffer is the
+    fixed-rate stream of the whole mean bucket and one decode of n values writes every shard. Variable rate:
+    gather_lengths (the one host read), allgather_padded of the streams (padded to an even word count: every shard's
+    stream starts 16-byte aligned), one all-gather of the indexes padded to a full shard's entry count, then one
+    decode per non-empty shard. A bf16 bucket receives the fp32 decode rounded to nearest even; other dtypes and
+    non-contiguous buckets go through an fp32 temporary. Ranks with empty shards join every collective with zero
+    words."""
+    codec = codec or device_codec()
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    bounds, _ = shard_plan(nvals, world)
+    lo, hi = bounds[rank]
+    dev = flat.device
+    direct = flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous()
+    out = flat if direct else torch.empty(nvals, dtype=torch.float32, device=dev)
+    nb = (nvals + 3) // 4
+    if params.minbits == params.maxbits:
+        pw = mean_stream_plan(nvals, world, params.maxbits)
+        local = torch.zeros(max(pw, 1), dtype=torch.int64, device=dev)
+        nw = ((hi - lo + 3) // 4 * params.maxbits + 63) // 64
+        if nw:
+            local[:nw] = words[:nw]
+        gathered = torch.zeros(world * local.numel() + 2, dtype=torch.int64, device=dev)  # + the decoders' slack
+        allgather_into(gathered[: world * local.numel()], local, group)
+        if nvals:
+            codec.decode(gathered, nvals, params, out=out)
+    else:
+        lens, lens_h = gather_lengths(bits if hi > lo else 0, dev, group)
+        maxw = max(2, (max((b + 63) // 64 for b in lens_h) + 1) // 2 * 2)
+        mine = words if hi > lo else torch.zeros(1, dtype=torch.int64, device=dev)
+        gathered = allgather_padded(mine, (lens_h[rank] + 63) // 64, maxw, group, pad=2)
+        per_b = max((b - a + 3) // 4 for a, b in bounds)
+        ni = max(1, (min(per_b, nb) + MEAN_INDEX_STRIDE - 1) // MEAN_INDEX_STRIDE)
+        nchunk = [((b - a + 3) // 4 + MEAN_INDEX_STRIDE - 1) // MEAN_INDEX_STRIDE for a, b in bounds]
+        imine = torch.zeros(ni, dtype=torch.int64, device=dev)
+        if nchunk[rank]:
+            imine[: nchunk[rank]] = index[: nchunk[rank]]
+        idx = torch.empty(world * ni, dtype=torch.int64, device=dev)
+        allgather_into(idx, imine, group)
+        for r, (a, b) in enumerate(bounds):
+            if b > a:
+                codec.decode(gathered[r * maxw:(r + 1) * maxw + 2], b - a, params, index=idx[r * ni:r * ni + nchunk[r]],
+                             index_stride=MEAN_INDEX_STRIDE, out=out[a:b])
+    if not direct:
+        flat.copy_(out.to(flat.dtype))
+    return flat
 
 
 def allgather_shards(flat: torch.Tensor, shard: torch.Tensor, nvals: int, group=None):

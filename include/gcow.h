@@ -359,6 +359,53 @@ gcow_status gcow_decode_mean_device(const zfp_input* field, const gcow_params* p
                                     void* hip_stream);
 
 /*
+ * W received streams straight into the stream of their mean (the sharded DDP hook's second stage: the mean shard
+ * travels compressed). field gives the shape only: 1-D, n values; field->data and field->dtype are ignored. The call
+ * is defined by two others:
+ *   1. m = what gcow_decode_mean_device writes into an fp32 field of n values from the same d_streams, streams_bytes,
+ *      stream_words, nstreams, d_index_in, index_words and index_stride_in under p_in:
+ *      ((0 + x_0) + x_1 + ...) / nstreams in fp32, no contraction.
+ *   2. d_err_out == NULL (d_err_in must be NULL too): d_out, *d_total_bits and d_index_out receive exactly what
+ *      gcow_encode_device of m under p_out writes. Otherwise they, and d_err_out, receive exactly what
+ *      gcow_encode_residual_device(m, d_err_in, d_err_out, ...) under p_out writes: y = m + e_in,
+ *      e_out = finite(y - decode(stream)); d_err_in == d_err_out (in place) is allowed, d_err_in NULL means zeros.
+ * Nothing is written past the stream's flushed words nor past e_out[n - 1]. Asynchronous on hip_stream: no
+ * allocation, no host synchronisation. n = 0 writes *d_total_bits = 0 and returns GCOW_OK.
+ * Two paths give that result (gcow_decode_mean_encode_path tells which one a call takes):
+ *   GCOW_MEANENC_FUSED_FIXED  p_in and p_out the same set, fixed rate with whole-word blocks (minbits == maxbits in
+ *      {32, 64}, maxprec >= 32, minexp <= -154; rate 8 and 16), no index in or out, error buffers 16-byte aligned: one
+ *      kernel (per block the W words decoded and summed in registers, the mean coded, the word stored and -- with
+ *      error buffers -- decoded from its register for e_out), plus a one-lane kernel for a partial last block. The
+ *      mean is never stored. No workspace.
+ *   GCOW_MEANENC_COMPOSED     every other legal call (any other fixed rate, p_in != p_out, variable rate with the
+ *      input index at stride 8, 16 or GCOW_INDEX_PACKED16, an output index, error buffers off 16-byte alignment):
+ *      gcow_decode_mean_device into n fp32 values at the head of the workspace, then gcow_encode_device or
+ *      gcow_encode_residual_device on that field with its own workspace behind.
+ * gcow_decode_mean_encode_workspace_bytes: 0 for the fused path (decided from the parameter sets alone: error buffers
+ * taken as aligned, no index), else 4 n rounded up to 256 plus the larger of the two inner calls' workspaces. A call
+ * that takes the composed path for its pointers' sake needs the composed size. d_workspace 16-byte aligned.
+ * Status codes follow the two calls: GCOW_ERR_INVALID when streams_bytes lacks the nstreams * stream_words + 2 words,
+ * for a wrong or missing input index, a short workspace, d_err_in without d_err_out; GCOW_ERR_CAPACITY when
+ * out_capacity < gcow_max_output_bytes of the fp32 field of n values under p_out; GCOW_ERR_UNSUPPORTED for dims != 1.
+ * gcow_decode_mean_encode_path: the path for these arguments, or -1 for a call that is refused. Pointers are inspected
+ * for presence (the indexes) and alignment (the error buffers) only, never dereferenced. All three functions decide
+ * through the same rule.
+ */
+enum { GCOW_MEANENC_COMPOSED = 0, GCOW_MEANENC_FUSED_FIXED = 1 };
+int gcow_decode_mean_encode_path(const zfp_input* field, const gcow_params* p_in, const gcow_params* p_out,
+                                 const float* d_err_in, const float* d_err_out, const uint64_t* d_index_in,
+                                 const uint64_t* d_index_out);
+size_t gcow_decode_mean_encode_workspace_bytes(const zfp_input* field, const gcow_params* p_in,
+                                               const gcow_params* p_out);
+gcow_status gcow_decode_mean_encode_device(const zfp_input* field, const gcow_params* p_in, const uint64_t* d_streams,
+                                           size_t streams_bytes, uint64_t stream_words, uint32_t nstreams,
+                                           const uint64_t* d_index_in, uint64_t index_words, uint32_t index_stride_in,
+                                           const gcow_params* p_out, const float* d_err_in, float* d_err_out,
+                                           void* d_out, size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                           size_t workspace_bytes, uint64_t* d_index_out, uint32_t index_stride_out,
+                                           void* hip_stream);
+
+/*
  * Packed 16-block index (index_stride GCOW_INDEX_PACKED16 in gcow_decode_mean_device): one uint64 per 16 blocks, the
  * low 48 bits the stream bit position of block 16 c (as the index every 16 blocks holds it), the high 16 bits the
  * offset of block 16 c + 8 from it (0 where that block does not exist). It carries the 8-block chunk starts at the
