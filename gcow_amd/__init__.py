@@ -6,7 +6,8 @@ memory, streams and torch.distributed (RCCL).
 """
 from ._ffi import GcowError, GcowParams, load  # noqa: F401
 
-__all__ = ["GcowError", "GcowParams", "load", "codec", "dist"]
+__all__ = ["GcowError", "GcowParams", "load", "codec", "dist", "TensorListRoundtrip", "roundtrip_tensors",
+           "roundtrip_gradients"]
 
 
 def __getattr__(name):
@@ -14,4 +15,7 @@ def __getattr__(name):
     if name in ("codec", "dist"):
         import importlib
         return importlib.import_module("." + name, __name__)
+    if name in ("TensorListRoundtrip", "roundtrip_tensors", "roundtrip_gradients"):
+        import importlib
+        return getattr(importlib.import_module(".codec", __name__), name)
     raise AttributeError(name)

@@ -60,6 +60,13 @@ class GcowParams(C.Structure):
         return self.tuple() == tuple(other.tuple() if hasattr(other, "tuple") else other)
 
 
+class RoundtripListStats(C.Structure):
+    """gcow_roundtrip_list_stats (include/gcow.h)."""
+    _fields_ = [("total_values", C.c_uint64), ("segments", C.c_uint64), ("direct_chunks", C.c_uint64),
+                ("gather_chunks", C.c_uint64), ("used_bytes", C.c_uint64), ("domain", C.c_uint32),
+                ("row_rule", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -107,6 +114,11 @@ def load():
         "gcow_encode_residual_device": (i32, [pi, pp, vp, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
         "gcow_encode_residual_path": (i32, [pi, pp, vp, vp, vp]),
         "gcow_roundtrip_device": (i32, [pi, pp, vp, i32, vp, vp]),
+        "gcow_roundtrip_list_plan_bytes": (sz, [sz, u64]),
+        "gcow_roundtrip_list_plan": (i32, [P(vp), P(vp), P(u64), sz, i32, i32, pp, vp, sz, P(sz)]),
+        "gcow_roundtrip_list_plan_stats": (i32, [vp, sz, P(RoundtripListStats)]),
+        "gcow_roundtrip_list_plan_chunk": (i32, [vp, sz, i32, u64, P(u64), P(u64), P(u64)]),
+        "gcow_roundtrip_list_device": (i32, [vp, vp, sz, pp, vp, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),

@@ -251,6 +251,157 @@ def roundtrip(x: torch.Tensor, params: GcowParams, out: torch.Tensor | None = No
     return out
 
 
+RTLIST_ROWS_DWORD, RTLIST_ROWS_NATURAL = 0, 1  # gcow_roundtrip_list_stats.row_rule
+
+
+class TensorListRoundtrip:
+    """roundtrip of the concatenation of a list of tensors, each read and written where it lies
+    (gcow_roundtrip_list_device): no torch.cat before the call, no copy per tensor after it. The object owns the host
+    plan (pinned) and its device copy; a call rebuilds and re-uploads them (non-blocking, on the call's stream) only
+    when the tuple of (data_ptr, numel) of the tensors, the dtypes or the device changes, so a training loop whose
+    gradients stay where they are plans once. `rebuilds` counts the plans made; `stats()` says how many chunks of
+    2048 blocks run through the direct kernels and how many through the gather kernel. One object serves one stream
+    at a time: a rebuild overwrites the device plan in stream order."""
+
+    def __init__(self, params: GcowParams):
+        self.L = load()
+        self.params = params
+        self.rebuilds = 0
+        self._key = None
+        self._h = None      # pinned int64 host plan
+        self._d = None      # its device copy
+        self._used = 0
+        self._uploaded = None  # event after the last upload: the host plan is not rewritten before it
+
+    @staticmethod
+    def _dt(t):
+        return DTYPE_BF16 if t == torch.bfloat16 else DTYPE_FLOAT
+
+    def _check(self, tensors, outs):
+        ok = (torch.float32, torch.bfloat16)
+        if outs is not None and len(outs) != len(tensors):
+            raise GcowError("roundtrip_tensors: %d outputs for %d tensors" % (len(outs), len(tensors)))
+        dev = None
+        for group, what in ((tensors, "tensors"), (outs or [], "outs")):
+            for t in group:
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise GcowError("roundtrip_tensors expects device tensors")
+                if t.dtype not in ok:
+                    raise GcowError("roundtrip_tensors: dtype %s not supported (float32, bfloat16)" % t.dtype)
+                if t.dtype != group[0].dtype:
+                    raise GcowError("roundtrip_tensors: %s of mixed dtypes (%s, %s)" % (what, group[0].dtype, t.dtype))
+                if not t.is_contiguous():
+                    raise GcowError("roundtrip_tensors expects contiguous tensors")
+                if dev is None:
+                    dev = t.device
+                elif t.device != dev:
+                    raise GcowError("roundtrip_tensors: tensors on different devices (%s, %s)" % (dev, t.device))
+        if outs is not None:
+            for t, o in zip(tensors, outs):
+                if o.numel() != t.numel():
+                    raise GcowError("roundtrip_tensors: an output of %d values for a tensor of %d" % (o.numel(),
+                                                                                                     t.numel()))
+        return dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _plan(self, tensors, outs, in_dt, out_dt, dev, stream):
+        n = len(tensors)
+        ins = (C.c_void_p * max(n, 1))(*[t.data_ptr() or None for t in tensors])
+        ous = (C.c_void_p * max(n, 1))(*[o.data_ptr() or None for o in outs]) if outs is not None else None
+        cnt = (C.c_uint64 * max(n, 1))(*[t.numel() for t in tensors])
+        need = self.L.gcow_roundtrip_list_plan_bytes(n, sum(t.numel() for t in tensors))
+        words = (need + 7) // 8
+        if self._uploaded is not None:
+            self._uploaded.synchronize()  # the pinned plan is still the source of a copy in flight
+        if self._h is None or self._h.numel() < words or self._d.device != dev:
+            self._h = torch.empty(words, dtype=torch.int64).pin_memory()
+            self._d = torch.empty(words, dtype=torch.int64, device=dev)
+        used = C.c_size_t(0)
+        check(self.L.gcow_roundtrip_list_plan(ins, ous, cnt, n, in_dt, out_dt, C.byref(self.params),
+                                              self._h.data_ptr(), self._h.numel() * 8, C.byref(used)),
+              "gcow_roundtrip_list_plan")
+        self._used = int(used.value)
+        w = (self._used + 7) // 8
+        with torch.cuda.stream(stream):
+            self._d[:w].copy_(self._h[:w], non_blocking=True)
+            self._uploaded = torch.cuda.Event()
+            self._uploaded.record(stream)
+        self.rebuilds += 1
+
+    def stats(self):
+        """gcow_roundtrip_list_stats of the current plan (None before the first call)."""
+        if self._h is None:
+            return None
+        from ._ffi import RoundtripListStats
+        s = RoundtripListStats()
+        check(self.L.gcow_roundtrip_list_plan_stats(self._h.data_ptr(), self._used, C.byref(s)),
+              "gcow_roundtrip_list_plan_stats")
+        return s
+
+    def __call__(self, tensors, outs=None, bits: torch.Tensor | None = None, stream=None):
+        tensors = list(tensors)
+        outs = list(outs) if outs is not None else None
+        dev = self._check(tensors, outs)
+        if bits is not None and not (bits.is_cuda and bits.device == dev and bits.dtype == torch.int64
+                                     and bits.numel() == 1):
+            raise GcowError("roundtrip_tensors: bits must be a one-element int64 tensor on the tensors' device")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        in_dt = self._dt(tensors[0].dtype) if tensors else DTYPE_FLOAT
+        out_dt = self._dt(outs[0].dtype) if outs else in_dt
+        key = (in_dt, out_dt, dev, tuple((t.data_ptr(), t.numel()) for t in tensors),
+               tuple(o.data_ptr() for o in outs) if outs is not None else None)
+        if key != self._key:
+            self._key = None
+            self._plan(tensors, outs, in_dt, out_dt, dev, stream)
+            self._key = key
+        check(self.L.gcow_roundtrip_list_device(self._h.data_ptr(), self._d.data_ptr(), self._used,
+                                                C.byref(self.params),
+                                                bits.data_ptr() if bits is not None else None, stream.cuda_stream),
+              "gcow_roundtrip_list_device")
+        return outs if outs is not None else tensors
+
+
+def roundtrip_tensors(tensors, params: GcowParams, outs=None, bits: torch.Tensor | None = None, stream=None,
+                      plan: TensorListRoundtrip | None = None):
+    """decode(encode(cat(tensors), params)) written back tensor by tensor, in one or two launches and without the
+    concatenation ever existing (gcow_roundtrip_list_device): tensor s receives values start_s .. start_s + n_s - 1
+    of codec.roundtrip(torch.cat([t.view(-1) for t in tensors]), params), bit for bit. tensors: contiguous fp32 or
+    bf16 device tensors of one dtype on one device (empty ones are skipped). outs: tensors of the same sizes and one
+    dtype (fp32 / bf16; bf16 is the fp32 decode rounded to nearest even); None runs in place. bits: optional int64[1]
+    device tensor that receives the bit length `encode` of the concatenation would report. plan: a TensorListRoundtrip
+    kept by the caller, so that repeated calls on tensors that stay where they are plan once; without it the call
+    plans every time. Returns the list of outputs."""
+    if plan is None:
+        plan = TensorListRoundtrip(params)
+    elif plan.params.tuple() != params.tuple():
+        raise GcowError("roundtrip_tensors: the plan object was made for %r" % (plan.params,))
+    return plan(tensors, outs, bits, stream)
+
+
+# roundtrip_gradients' plan objects, one per (parameter set, device): visible so that a caller can drop them
+# (gradient_plans.clear()) or read their stats()
+gradient_plans: dict = {}
+
+
+def roundtrip_gradients(parameters, params: GcowParams, bits: torch.Tensor | None = None, stream=None,
+                        cache: dict | None = None) -> TensorListRoundtrip:
+    """The reference's collect_gradients -> compress -> decompress -> assign_gradients
+    (hw/models/train_imagenet.py:448-475) as one call: p.grad of every parameter that has one, in iteration order (the
+    order collect_gradients concatenates them in), round-tripped in place as one field. The plan object lives in
+    `cache` (default: codec.gradient_plans) under the parameter set and device, so a training loop whose .grad tensors
+    stay where they are pays for the plan once. Returns the plan object (stats(), rebuilds)."""
+    grads = [q.grad for q in parameters if q.grad is not None]
+    if cache is None:
+        cache = gradient_plans
+    dev = grads[0].device if grads else None
+    key = (params.tuple(), str(dev))
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = TensorListRoundtrip(params)
+    plan(grads, None, bits, stream)
+    return plan
+
+
 def field_of_shape(shape, dtype) -> ZfpInput:
     f = ZfpInput()
     f.dtype = DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_FLOAT

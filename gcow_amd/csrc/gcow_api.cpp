@@ -974,6 +974,201 @@ gcow_status gcow_roundtrip_device(const zfp_input* field, const gcow_params* p, 
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- round trip, tensor list
+// Rows of a direct chunk must start at a multiple of this many bytes: 4 (multi-dword buffer accesses are dword-aligned),
+// for either element type. GCOW_RTL_NATURAL_ROWS builds the fallback rule instead: the row's own size, 16 bytes (fp32)
+// or 8 (bf16).
+#ifdef GCOW_RTL_NATURAL_ROWS
+static const uint32_t kRtlRule = GCOW_RTLIST_ROWS_NATURAL;
+#else
+static const uint32_t kRtlRule = GCOW_RTLIST_ROWS_DWORD;
+#endif
+
+static size_t rtl_row_align(size_t esz) { return kRtlRule == GCOW_RTLIST_ROWS_DWORD ? 4 : 4 * esz; }
+
+static const size_t kRtlHeaderBytes = (sizeof(gcow::RtListHeader) + 15) / 16 * 16;
+
+size_t gcow_roundtrip_list_plan_bytes(size_t nsegs, uint64_t total_values)
+{
+  const uint64_t nblocks = total_values / 4 + (total_values % 4 ? 1 : 0);
+  const uint64_t nchunks = (nblocks + gcow::kRtListChunkBlocks - 1) / gcow::kRtListChunkBlocks;
+  // every chunk is one descriptor of the larger kind at most; every segment one entry, and the sentinel
+  return kRtlHeaderBytes + (size_t)nchunks * sizeof(gcow::RtListDirect) + (nsegs + 1) * sizeof(gcow::RtListSeg);
+}
+
+static int rtl_domain(const gcow_params& p)
+{
+  if (resid_lean_params(p)) return gcow::kRoundtripLean;
+  if (p.minbits <= 1 && p.maxbits >= 160) return gcow::kRoundtripVar;
+  return gcow::kRoundtripGeneric;
+}
+
+gcow_status gcow_roundtrip_list_plan(const void* const* in_ptrs, void* const* out_ptrs, const uint64_t* counts,
+                                     size_t nsegs, data_type in_dtype, data_type out_dtype, const gcow_params* p,
+                                     void* h_plan, size_t plan_bytes, size_t* used_bytes)
+{
+  if (!p) return fail(GCOW_ERR_INVALID, "null params");
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan buffer");
+  if (nsegs && (!in_ptrs || !counts)) return fail(GCOW_ERR_INVALID, "null pointer or count array");
+  if (in_dtype != dtype_float && in_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip supports dtype_float and dtype_bf16 fields");
+  if (out_dtype != dtype_float && out_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip writes dtype_float or dtype_bf16");
+  if (!out_ptrs && in_dtype != out_dtype)
+    return fail(GCOW_ERR_INVALID, "in place (out_ptrs NULL) needs equal dtypes");
+  gcow_status st = check_params(p, 1);
+  if (st) return st;
+  const size_t ei = in_dtype == dtype_bf16 ? 2 : 4, eo = out_dtype == dtype_bf16 ? 2 : 4;
+  uint64_t nvals = 0;
+  size_t nlive = 0;
+  for (size_t s = 0; s < nsegs; s++) {
+    if (!counts[s]) continue;
+    const void* ip = in_ptrs[s];
+    const void* op = out_ptrs ? out_ptrs[s] : in_ptrs[s];
+    if (!ip || !op) return fail(GCOW_ERR_INVALID, "null tensor pointer with a non-zero count");
+    if ((uintptr_t)ip % ei || (uintptr_t)op % eo) return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+    if (counts[s] >= (1ull << 34) || nvals + counts[s] > (1ull << 34) - 4)
+      return fail(GCOW_ERR_UNSUPPORTED, "more than 2^32 blocks per call");
+    nvals += counts[s];
+    nlive++;
+  }
+  if (plan_bytes < gcow_roundtrip_list_plan_bytes(nlive, nvals))
+    return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_roundtrip_list_plan_bytes()");
+  if ((uintptr_t)h_plan % 8) return fail(GCOW_ERR_INVALID, "misaligned plan buffer");
+
+  char* base = (char*)h_plan;
+  gcow::RtListHeader H;
+  std::memset(&H, 0, sizeof(H));
+  H.magic = gcow::kRtListMagic;
+  H.domain = (uint32_t)rtl_domain(*p);
+  H.in_dtype = in_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32;
+  H.out_dtype = out_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32;
+  H.nsegs = (uint32_t)nlive;
+  H.nvals = nvals;
+  H.params[0] = p->minbits, H.params[1] = p->maxbits, H.params[2] = p->maxprec, H.params[3] = (uint32_t)p->minexp;
+
+  // the segment table first (in a scratch vector: its place in the plan is behind the two chunk tables)
+  std::vector<gcow::RtListSeg> segs;
+  segs.reserve(nlive + 1);
+  uint64_t at = 0;
+  for (size_t s = 0; s < nsegs; s++) {
+    if (!counts[s]) continue;
+    segs.push_back({at, (uint64_t)(uintptr_t)in_ptrs[s], (uint64_t)(uintptr_t)(out_ptrs ? out_ptrs[s] : in_ptrs[s])});
+    at += counts[s];
+  }
+  segs.push_back({nvals, 0, 0});
+
+  const uint64_t CV = 4ull * gcow::kRtListChunkBlocks;
+  const uint64_t nchunks = (nvals + CV - 1) / CV;
+  std::vector<gcow::RtListDirect> dir;
+  std::vector<gcow::RtListGather> gat;
+  const size_t ra_in = rtl_row_align(ei), ra_out = rtl_row_align(eo);
+  size_t lo = 0;
+  for (uint64_t c = 0; c < nchunks; c++) {
+    const uint64_t v0 = c * CV, v1 = std::min(v0 + CV, nvals);
+    while (segs[lo + 1].start <= v0) lo++;
+    size_t hi = lo;
+    while (segs[hi + 1].start < v1) hi++;
+    bool direct = H.domain != (uint32_t)gcow::kRoundtripGeneric && lo == hi && (v1 - v0) % 4 == 0;
+    uint64_t ia = 0, oa = 0;
+    if (direct) {
+      ia = segs[lo].in + (v0 - segs[lo].start) * ei;
+      oa = segs[lo].out + (v0 - segs[lo].start) * eo;
+      direct = ia % ra_in == 0 && oa % ra_out == 0;
+    }
+    if (direct) dir.push_back({ia, oa, (uint32_t)((v1 - v0) / 4), 0u});
+    else gat.push_back({(uint32_t)(v0 / 4), (uint32_t)lo, (uint32_t)hi, 0u});
+  }
+  H.ndirect = (uint32_t)dir.size();
+  H.ngather = (uint32_t)gat.size();
+  H.off_direct = kRtlHeaderBytes;
+  H.off_gather = H.off_direct + dir.size() * sizeof(gcow::RtListDirect);
+  H.off_segs = H.off_gather + gat.size() * sizeof(gcow::RtListGather);
+  H.bytes = H.off_segs + segs.size() * sizeof(gcow::RtListSeg);
+  if (H.bytes > plan_bytes) return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_roundtrip_list_plan_bytes()");
+  std::memcpy(base, &H, sizeof(H));
+  if (!dir.empty()) std::memcpy(base + H.off_direct, dir.data(), dir.size() * sizeof(gcow::RtListDirect));
+  if (!gat.empty()) std::memcpy(base + H.off_gather, gat.data(), gat.size() * sizeof(gcow::RtListGather));
+  std::memcpy(base + H.off_segs, segs.data(), segs.size() * sizeof(gcow::RtListSeg));
+  if (used_bytes) *used_bytes = (size_t)H.bytes;
+  return GCOW_OK;
+}
+
+// The header of a host plan, checked against the buffer's size
+static gcow_status rtl_header(const void* h_plan, size_t plan_bytes, gcow::RtListHeader& H)
+{
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan");
+  if (plan_bytes < sizeof(H)) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  std::memcpy(&H, h_plan, sizeof(H));
+  if (H.magic != gcow::kRtListMagic) return fail(GCOW_ERR_INVALID, "not a plan of gcow_roundtrip_list_plan");
+  if (plan_bytes < H.bytes) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_list_plan_stats(const void* h_plan, size_t plan_bytes, gcow_roundtrip_list_stats* stats)
+{
+  gcow::RtListHeader H;
+  gcow_status st = rtl_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!stats) return fail(GCOW_ERR_INVALID, "null stats");
+  stats->total_values = H.nvals;
+  stats->segments = H.nsegs;
+  stats->direct_chunks = H.ndirect;
+  stats->gather_chunks = H.ngather;
+  stats->domain = H.domain;
+  stats->row_rule = kRtlRule;
+  stats->used_bytes = H.bytes;
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_list_plan_chunk(const void* h_plan, size_t plan_bytes, int gather, uint64_t i,
+                                           uint64_t* a, uint64_t* b, uint64_t* c)
+{
+  gcow::RtListHeader H;
+  gcow_status st = rtl_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!a || !b || !c) return fail(GCOW_ERR_INVALID, "null result pointer");
+  if (i >= (gather ? H.ngather : H.ndirect)) return fail(GCOW_ERR_INVALID, "chunk index out of range");
+  const char* base = (const char*)h_plan;
+  if (gather) {
+    gcow::RtListGather g;
+    std::memcpy(&g, base + H.off_gather + i * sizeof(g), sizeof(g));
+    *a = g.b0, *b = g.seg_lo, *c = g.seg_hi;
+  } else {
+    gcow::RtListDirect d;
+    std::memcpy(&d, base + H.off_direct + i * sizeof(d), sizeof(d));
+    *a = d.in, *b = d.out, *c = d.nb;
+  }
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_list_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const gcow_params* p,
+                                       uint64_t* d_total_bits, void* hip_stream)
+{
+  if (!p) return fail(GCOW_ERR_INVALID, "null params");
+  gcow::RtListHeader H;
+  gcow_status st = rtl_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if ((st = check_params(p, 1))) return st;
+  if (H.params[0] != p->minbits || H.params[1] != p->maxbits || H.params[2] != p->maxprec ||
+      H.params[3] != (uint32_t)p->minexp)
+    return fail(GCOW_ERR_INVALID, "the plan was made for other parameters");
+  if ((uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "misaligned d_total_bits");
+  if (H.nvals == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  const bool fixed = p->minbits == p->maxbits;
+  uint64_t* total = nullptr;  // variable rate: the kernels add every block's length
+  if (d_total_bits) {
+    GCOW_HIP(gcow::launch_set_u64(d_total_bits, fixed ? (H.nvals + 3) / 4 * p->maxbits : 0, hip_stream));
+    if (!fixed) total = d_total_bits;
+  }
+  GCOW_HIP(gcow::launch_roundtrip_list1d(H, d_plan, P(*p), total, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

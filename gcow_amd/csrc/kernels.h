@@ -109,6 +109,37 @@ hipError_t launch_resid_finish(const float* y, float* e, uint64_t nvals, void* s
 enum { kRoundtripLean = 0, kRoundtripVar = 1, kRoundtripGeneric = 2 };
 hipError_t launch_roundtrip1d(const void* in, int in_dtype, uint64_t nvals, const Params& p, int domain, void* out,
                               int out_dtype, uint64_t* total, void* stream);
+// Round trip over a tensor list (roundtrip_list1d.hip): the field X is the concatenation of the plan's segments. The
+// plan (gcow_roundtrip_list_plan, gcow_api.cpp) is one buffer: RtListHeader, then ndirect RtListDirect, ngather
+// RtListGather and nsegs + 1 RtListSeg (the last one a sentinel: start = nvals). A chunk is 256 * GCOW_RT_U blocks of
+// X (kRtListChunkBlocks; roundtrip_list1d.hip asserts the two agree).
+constexpr uint32_t kRtListChunkBlocks = 2048;
+constexpr uint32_t kRtListMagic = 0x4c545267u;  // "gRTL"
+struct RtListDirect {  // a chunk whose nb whole blocks lie in one segment, rows at 4-byte aligned addresses
+  uint64_t in, out;    // the chunk's first row
+  uint32_t nb, pad;
+};
+struct RtListGather {  // any other chunk: blocks b0 .. min(b0 + kRtListChunkBlocks, nblocks) - 1 of X
+  uint32_t b0;
+  uint32_t seg_lo, seg_hi;  // the segments holding the chunk's first and last value
+  uint32_t pad;
+};
+struct RtListSeg {  // a non-empty segment: values start .. next start - 1 of X
+  uint64_t start, in, out;
+};
+struct RtListHeader {
+  uint32_t magic, domain;  // kRoundtrip*
+  uint32_t in_dtype, out_dtype;
+  uint32_t nsegs, ndirect, ngather, pad;
+  uint64_t nvals;
+  uint32_t params[4];
+  uint64_t off_direct, off_gather, off_segs, bytes;  // byte offsets into the plan; bytes = the plan's used size
+};
+static_assert(sizeof(RtListDirect) == 24 && sizeof(RtListGather) == 16 && sizeof(RtListSeg) == 24 &&
+              sizeof(RtListHeader) == 88, "plan layout");
+// h: the plan's header (HOST copy); d_plan: the whole plan on the DEVICE. total as launch_roundtrip1d's.
+hipError_t launch_roundtrip_list1d(const RtListHeader& h, const void* d_plan, const Params& p, uint64_t* total,
+                                   void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

@@ -312,6 +312,70 @@ gcow_status gcow_roundtrip_device(const zfp_input* field, const gcow_params* p, 
                                   uint64_t* d_total_bits, void* hip_stream);
 
 /*
+ * Round trip over a tensor list: the gradients where they lie, without the torch.cat before gcow_roundtrip_device and
+ * the copy per parameter after it (the reference's collect_gradients / assign_gradients, hw/models/
+ * train_imagenet.py:448-475). Let X = cat(t_0 ... t_{S-1}) be the 1-D field of N values. After the call out_s holds
+ * roundtrip(X)[start_s : start_s + n_s], bit for bit what gcow_roundtrip_device writes for the contiguous X under the
+ * same parameters and dtypes: blocks are X's blocks (a block may take its four values from up to four tensors), the
+ * last block is padded as there, only real values are written and nothing outside [out_s, out_s + n_s) is.
+ * All inputs share in_dtype and all outputs out_dtype (dtype_float or dtype_bf16, in any combination). out_s == in_s
+ * is allowed when the dtypes are equal (in place: the normal use); any other overlap between any two buffers of the
+ * call is undefined.
+ *
+ * The device call allocates nothing and never synchronises, so the address arithmetic is prepared on the host, once
+ * per list, as a PLAN whose layout is private to the library:
+ *   gcow_roundtrip_list_plan_bytes(nsegs, total_values): the size of a plan of nsegs tensors holding total_values
+ *     values together (an upper bound: the plan drops empty tensors and gcow_roundtrip_list_plan reports what it used).
+ *   gcow_roundtrip_list_plan: fills the caller's HOST buffer h_plan (8-byte aligned, plan_bytes long). in_ptrs /
+ *     out_ptrs / counts: HOST arrays of nsegs DEVICE pointers and value counts; out_ptrs == NULL means in place (equal
+ *     dtypes). *used_bytes (optional) = the bytes the caller copies to the device. The plan cuts X into chunks of 2048
+ *     blocks (8192 values, the fused kernels' workgroup chunk) and records each as one of two kinds:
+ *       direct: all its blocks are whole and lie inside one tensor, and its first row's input and output addresses are
+ *               multiples of 4 bytes (GCOW_RTLIST_ROWS_DWORD: multi-dword buffer accesses are dword-aligned, so fp32
+ *               rows always qualify and bf16 rows do at an even element offset; a tensor that starts at a flat offset
+ *               that is no multiple of 4 still runs direct). One workgroup runs gcow_roundtrip_device's block
+ *               sequence on it unchanged.
+ *       gather: everything else -- a seam between tensors, rows off that alignment, the chunk holding the partial last
+ *               block. Each value is located in the plan's tensor table and loaded on its own; blocks go through the
+ *               same block functions, so the result is the same bits.
+ *     The domain is picked once from the parameters as gcow_roundtrip_device picks it (whole-word fixed rate; no
+ *     budget: minbits <= 1 and maxbits >= 160; else generic). In the generic domain every chunk is a gather chunk.
+ *   gcow_roundtrip_list_plan_stats: what a plan holds (tests and the timing tool see which path runs).
+ *   gcow_roundtrip_list_plan_chunk: TEST / MEASUREMENT ONLY: descriptor i of the direct (gather = 0: *a, *b = the
+ *     first row's input and output address, *c = blocks) or gather (*a = first block, *b, *c = the indices, among the
+ *     non-empty tensors, of those holding the chunk's first and last value) chunks.
+ *   gcow_roundtrip_list_device: the launches. h_plan: the HOST plan (its header holds the launch geometry, which is
+ *     why the call needs no synchronisation); d_plan: the caller's DEVICE copy of its first used_bytes bytes, 8-byte
+ *     aligned, copied on hip_stream or complete before the call. p must be the plan's parameter set. *d_total_bits
+ *     (optional, DEVICE uint64) = what gcow_encode_device(X) would report: nblocks * maxbits at fixed rate, else the
+ *     sum of the block lengths. Asynchronous on hip_stream. N = 0 writes *d_total_bits = 0 and returns GCOW_OK. The
+ *     plan is valid as long as the tensors stay where they are.
+ * GCOW_ERR_UNSUPPORTED: a dtype other than float / bf16; 2^32 blocks or more in X. GCOW_ERR_INVALID: NULL p or
+ * h_plan; a NULL or misaligned (for its element type) pointer with a non-zero count; out_ptrs NULL with unequal
+ * dtypes; plan_bytes too small (plan: for the list; stats, device: for the plan); a device call whose p differs from
+ * the plan's; misaligned d_plan or d_total_bits; check_params as in gcow_encode_device.
+ */
+enum { GCOW_RTLIST_ROWS_DWORD = 0, GCOW_RTLIST_ROWS_NATURAL = 1 };
+typedef struct {
+  uint64_t total_values;  /* N */
+  uint64_t segments;      /* non-empty tensors */
+  uint64_t direct_chunks;
+  uint64_t gather_chunks;
+  uint64_t used_bytes;    /* the plan's size */
+  uint32_t domain;        /* 0 whole-word fixed rate, 1 no budget, 2 generic */
+  uint32_t row_rule;      /* GCOW_RTLIST_ROWS_*: the alignment rule direct chunks were held to */
+} gcow_roundtrip_list_stats;
+size_t gcow_roundtrip_list_plan_bytes(size_t nsegs, uint64_t total_values);
+gcow_status gcow_roundtrip_list_plan(const void* const* in_ptrs, void* const* out_ptrs, const uint64_t* counts,
+                                     size_t nsegs, data_type in_dtype, data_type out_dtype, const gcow_params* p,
+                                     void* h_plan, size_t plan_bytes, size_t* used_bytes);
+gcow_status gcow_roundtrip_list_plan_stats(const void* h_plan, size_t plan_bytes, gcow_roundtrip_list_stats* stats);
+gcow_status gcow_roundtrip_list_plan_chunk(const void* h_plan, size_t plan_bytes, int gather, uint64_t i, uint64_t* a,
+                                           uint64_t* b, uint64_t* c);
+gcow_status gcow_roundtrip_list_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
+                                       const gcow_params* p, uint64_t* d_total_bits, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by

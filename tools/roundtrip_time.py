@@ -8,8 +8,21 @@ driver protocol (5 untimed + 20 timed launches, mean HIP-event time: "cold") and
 back-to-back launches, 50 launches). One JSON line per config; the fused call's bytes/s counts input plus output bytes
 per value, from the shapes. faster_*: the fused form beats the faster composed run by more than the composed form's
 spread.
-usage: roundtrip_time.py [--log2n 28] [--only NAME]"""
+usage: roundtrip_time.py [--log2n 28] [--only NAME]
+
+--list: the round trip over a tensor list instead (codec.roundtrip_tensors -> gcow_roundtrip_list_device), on a
+ResNet-50-shaped fp32 list made here from the architecture's layer recipe (161 tensors, 25.6 M values, each tensor its
+own allocation as .grad tensors are), at rate 16 and accuracy 1e-3. Form A is the flow the list call replaces:
+torch.cat into a preallocated flat buffer, codec.roundtrip in place on it, one copy_ per tensor back. Form B is
+roundtrip_tensors in place with a kept plan object. Both run on the same tensors; they must leave identical bits and
+bit counts (checked first, on clones); then A, B and A again are timed, cold and steady, as above. The list with one
+scalar tensor put first -- every later row of the field then lies off 16-byte alignment in its tensor -- is timed too.
+single_*: B on one tensor of the same total against plain codec.roundtrip in place on it, the price of the chunk
+descriptors. Each line reports the plan's direct / gather chunk counts. not_slower_*: B is not slower than the faster A
+run by more than A's own run-to-run spread.
+usage: roundtrip_time.py --list [--only NAME]"""
 import json
+import math
 import os
 import sys
 import time
@@ -62,6 +75,100 @@ def cold_and_steady(fn):
         torch.cuda.synchronize()
     return cold, timed(fn, 0, 50)
 
+
+def resnet50_shapes():
+    """The parameter shapes of ResNet-50 in module order (conv, then its batch norm's weight and bias; the
+    downsample path after a stage's first bottleneck; the classifier last)."""
+    shapes = [(64, 3, 7, 7), (64,), (64,)]
+    inplanes = 64
+    for planes, blocks in ((64, 3), (128, 4), (256, 6), (512, 3)):
+        for b in range(blocks):
+            shapes += [(planes, inplanes, 1, 1), (planes,), (planes,), (planes, planes, 3, 3), (planes,), (planes,),
+                       (4 * planes, planes, 1, 1), (4 * planes,), (4 * planes,)]
+            if b == 0:
+                shapes += [(4 * planes, inplanes, 1, 1), (4 * planes,), (4 * planes,)]
+            inplanes = 4 * planes
+    return shapes + [(1000, 2048), (1000,)]
+
+
+def list_leg():
+    shapes = resnet50_shapes()
+    lists = {"resnet50": shapes, "resnet50_scalar_first": [()] + shapes, "single": [(sum(math.prod(s) for s in shapes),)]}
+    configs = [("fp32_rate16", codec.rate(16, 1)), ("fp32_acc1e-3", codec.accuracy(1e-3))]
+    for lname, shp in lists.items():
+        total = sum(math.prod(s) for s in shp)
+        src = torch.empty(total, dtype=torch.float32, device="cuda")
+        codec.fill_normal(src, 1e-3, seed=0x67636F77, inject=True)
+        offs = [0]
+        for s in shp:
+            offs.append(offs[-1] + math.prod(s))
+
+        def fresh():
+            return [src[offs[i]:offs[i + 1]].clone().view(s) for i, s in enumerate(shp)]
+
+        for cname, p in configs:
+            name = "list_%s_%s" % (lname, cname)
+            if only and name != only:
+                continue
+            fixed = codec.is_fixed(p)
+            flat = torch.empty(total, dtype=torch.float32, device="cuda")
+            bits_a = torch.zeros(1, dtype=torch.int64, device="cuda")
+            bits_b = torch.zeros(1, dtype=torch.int64, device="cuda")
+            plan = codec.TensorListRoundtrip(p)
+
+            def form_a(ts, views, backs):
+                torch.cat(views, out=flat)
+                codec.roundtrip(flat, p, out=flat, bits=None if fixed else bits_a, stream=st)
+                for t, b in zip(ts, backs):
+                    t.copy_(b)
+
+            def bind(ts):
+                return ts, [t.view(-1) for t in ts], [flat[offs[i]:offs[i + 1]].view(s) for i, s in enumerate(shp)]
+
+            # the same bits first, on clones
+            ta, tb = fresh(), fresh()
+            form_a(*bind(ta))
+            codec.roundtrip_tensors(tb, p, bits=None if fixed else bits_b, stream=st)
+            torch.cuda.synchronize()
+            same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(ta, tb))
+            if not fixed:
+                same = same and int(bits_a.item()) == int(bits_b.item())
+            del ta, tb
+            ts = fresh()
+            bound = bind(ts)
+
+            def a_fn():
+                form_a(*bound)
+
+            def b_fn():
+                codec.roundtrip_tensors(ts, p, bits=None if fixed else bits_b, stream=st, plan=plan)
+
+            def r_fn():  # single: the contiguous call in place
+                codec.roundtrip(ts[0], p, out=ts[0], bits=None if fixed else bits_a, stream=st)
+
+            base = r_fn if lname == "single" else a_fn
+            b_fn()
+            stats = plan.stats()
+            res = {"config": name, "tensors": len(shp), "n": total, "same_result": same,
+                   "direct_chunks": int(stats.direct_chunks), "gather_chunks": int(stats.gather_chunks),
+                   "gather_share": round(stats.gather_chunks / max(1, stats.direct_chunks + stats.gather_chunks), 4),
+                   "row_rule": int(stats.row_rule), "baseline": "roundtrip" if lname == "single" else "cat_roundtrip_copy"}
+            a1 = cold_and_steady(base)
+            b = cold_and_steady(b_fn)
+            a2 = cold_and_steady(base)
+            for k, i in (("cold", 0), ("steady", 1)):
+                res["list_%s_ms" % k] = round(b[i], 4)
+                res["baseline_%s_ms" % k] = [round(a1[i], 4), round(a2[i], 4)]
+                res["baseline_over_list_%s" % k] = round(min(a1[i], a2[i]) / b[i], 3)
+                res["not_slower_%s" % k] = bool(b[i] - min(a1[i], a2[i]) <= abs(a1[i] - a2[i]))
+            res["plan_rebuilds"] = plan.rebuilds
+            print(json.dumps(res), flush=True)
+            del ts, bound, flat
+
+
+if "--list" in sys.argv:
+    list_leg()
+    sys.exit(0)
 
 x32 = torch.empty(n, dtype=torch.float32, device="cuda")
 codec.fill_normal(x32, 1e-3, seed=0x67636F77, inject=True)
