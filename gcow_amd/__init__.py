@@ -7,7 +7,7 @@ memory, streams and torch.distributed (RCCL).
 from ._ffi import GcowError, GcowParams, load  # noqa: F401
 
 __all__ = ["GcowError", "GcowParams", "load", "codec", "dist", "TensorListRoundtrip", "roundtrip_tensors",
-           "roundtrip_gradients"]
+           "roundtrip_gradients", "TensorListRelative", "roundtrip_tensors_relative", "roundtrip_gradients_relative"]
 
 
 def __getattr__(name):
@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ("codec", "dist"):
         import importlib
         return importlib.import_module("." + name, __name__)
-    if name in ("TensorListRoundtrip", "roundtrip_tensors", "roundtrip_gradients"):
+    if name in ("TensorListRoundtrip", "roundtrip_tensors", "roundtrip_gradients", "TensorListRelative",
+                "roundtrip_tensors_relative", "roundtrip_gradients_relative"):
         import importlib
         return getattr(importlib.import_module(".codec", __name__), name)
     raise AttributeError(name)

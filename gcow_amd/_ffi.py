@@ -67,6 +67,12 @@ class RoundtripListStats(C.Structure):
                 ("row_rule", C.c_uint32)]
 
 
+class RoundtripRelStats(C.Structure):
+    """gcow_roundtrip_rel_stats (include/gcow.h)."""
+    _fields_ = [("total_values", C.c_uint64), ("total_blocks", C.c_uint64), ("segments", C.c_uint64),
+                ("direct_chunks", C.c_uint64), ("gather_chunks", C.c_uint64), ("used_bytes", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -119,6 +125,11 @@ def load():
         "gcow_roundtrip_list_plan_stats": (i32, [vp, sz, P(RoundtripListStats)]),
         "gcow_roundtrip_list_plan_chunk": (i32, [vp, sz, i32, u64, P(u64), P(u64), P(u64)]),
         "gcow_roundtrip_list_device": (i32, [vp, vp, sz, pp, vp, vp]),
+        "gcow_roundtrip_rel_plan_bytes": (sz, [sz, u64]),
+        "gcow_roundtrip_rel_plan": (i32, [P(vp), P(vp), P(u64), sz, i32, i32, vp, sz, P(sz)]),
+        "gcow_roundtrip_rel_plan_stats": (i32, [vp, sz, P(RoundtripRelStats)]),
+        "gcow_roundtrip_rel_plan_chunk": (i32, [vp, sz, i32, u64, P(u64), P(u64), P(u64)]),
+        "gcow_roundtrip_rel_device": (i32, [vp, vp, sz, u32, u32, vp, vp, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),

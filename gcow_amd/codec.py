@@ -402,6 +402,129 @@ def roundtrip_gradients(parameters, params: GcowParams, bits: torch.Tensor | Non
     return plan
 
 
+REL_BITS_MAX = 24  # gcow_roundtrip_rel_device's range of rel_bits
+
+
+class TensorListRelative(TensorListRoundtrip):
+    """The round trip of every tensor of a list as a field of its own, under a tolerance relative to that tensor
+    (gcow_roundtrip_rel_device): tensor s is coded in accuracy mode with minexp_s = max(emax_s - rel_bits, -94)
+    (capped for a maximum in the top binade so that the decode stays finite: include/gcow.h), emax_s the exponent of
+    its largest finite magnitude, which the call finds on the device, so that
+    |out - t| <= 2^minexp_s < 2^(1 - rel_bits) max|t_s|. Mirrors TensorListRoundtrip: the object owns the pinned host
+    plan and its device copy and re-plans only when the pointers, counts, dtypes or device change (the plan depends on
+    neither rel_bits nor maxprec); `rebuilds` counts the plans made, `stats()` gives gcow_roundtrip_rel_stats.
+    `absmax` is the float32 tensor of the last call's per-tensor maxima (the caller's, or one kept here)."""
+
+    def __init__(self, rel_bits: int, maxprec: int = 64):
+        super().__init__(None)
+        self.rel_bits, self.maxprec = int(rel_bits), int(maxprec)
+        self.absmax = None
+
+    def _plan(self, tensors, outs, in_dt, out_dt, dev, stream):
+        n = len(tensors)
+        ins = (C.c_void_p * max(n, 1))(*[t.data_ptr() or None for t in tensors])
+        ous = (C.c_void_p * max(n, 1))(*[o.data_ptr() or None for o in outs]) if outs is not None else None
+        cnt = (C.c_uint64 * max(n, 1))(*[t.numel() for t in tensors])
+        need = self.L.gcow_roundtrip_rel_plan_bytes(n, sum(t.numel() for t in tensors))
+        words = (need + 7) // 8
+        if self._uploaded is not None:
+            self._uploaded.synchronize()  # the pinned plan is still the source of a copy in flight
+        if self._h is None or self._h.numel() < words or self._d.device != dev:
+            self._h = torch.empty(words, dtype=torch.int64).pin_memory()
+            self._d = torch.empty(words, dtype=torch.int64, device=dev)
+        used = C.c_size_t(0)
+        check(self.L.gcow_roundtrip_rel_plan(ins, ous, cnt, n, in_dt, out_dt, self._h.data_ptr(),
+                                             self._h.numel() * 8, C.byref(used)), "gcow_roundtrip_rel_plan")
+        self._used = int(used.value)
+        w = (self._used + 7) // 8
+        with torch.cuda.stream(stream):
+            self._d[:w].copy_(self._h[:w], non_blocking=True)
+            self._uploaded = torch.cuda.Event()
+            self._uploaded.record(stream)
+        self.rebuilds += 1
+
+    def stats(self):
+        """gcow_roundtrip_rel_stats of the current plan (None before the first call)."""
+        if self._h is None:
+            return None
+        from ._ffi import RoundtripRelStats
+        s = RoundtripRelStats()
+        check(self.L.gcow_roundtrip_rel_plan_stats(self._h.data_ptr(), self._used, C.byref(s)),
+              "gcow_roundtrip_rel_plan_stats")
+        return s
+
+    def __call__(self, tensors, outs=None, absmax: torch.Tensor | None = None, bits: torch.Tensor | None = None,
+                 stream=None):
+        tensors = list(tensors)
+        outs = list(outs) if outs is not None else None
+        dev = self._check(tensors, outs)
+        n = len(tensors)
+        if bits is not None and not (bits.is_cuda and bits.device == dev and bits.dtype == torch.int64
+                                     and bits.numel() == 1):
+            raise GcowError("roundtrip_tensors_relative: bits must be a one-element int64 tensor on the tensors' device")
+        if absmax is None:
+            if self.absmax is None or self.absmax.numel() != n or self.absmax.device != dev:
+                self.absmax = torch.zeros(n, dtype=torch.float32, device=dev)
+            absmax = self.absmax
+        elif not (absmax.is_cuda and absmax.device == dev and absmax.dtype == torch.float32
+                  and absmax.is_contiguous() and absmax.numel() == n):
+            raise GcowError("roundtrip_tensors_relative: absmax must be a contiguous float32 tensor of len(tensors) "
+                            "values on the tensors' device")
+        else:
+            self.absmax = absmax
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        in_dt = self._dt(tensors[0].dtype) if tensors else DTYPE_FLOAT
+        out_dt = self._dt(outs[0].dtype) if outs else in_dt
+        key = (in_dt, out_dt, dev, tuple((t.data_ptr(), t.numel()) for t in tensors),
+               tuple(o.data_ptr() for o in outs) if outs is not None else None)
+        if key != self._key:
+            self._key = None
+            self._plan(tensors, outs, in_dt, out_dt, dev, stream)
+            self._key = key
+        check(self.L.gcow_roundtrip_rel_device(self._h.data_ptr(), self._d.data_ptr(), self._used, self.rel_bits,
+                                               self.maxprec, absmax.data_ptr() if n else None,
+                                               bits.data_ptr() if bits is not None else None, stream.cuda_stream),
+              "gcow_roundtrip_rel_device")
+        return outs if outs is not None else tensors
+
+
+def roundtrip_tensors_relative(tensors, rel_bits: int, outs=None, absmax: torch.Tensor | None = None,
+                               bits: torch.Tensor | None = None, stream=None,
+                               plan: TensorListRelative | None = None, maxprec: int = 64):
+    """Every tensor round-tripped where it lies under a tolerance relative to its own largest magnitude
+    (gcow_roundtrip_rel_device): tensor s receives codec.roundtrip(t_s, expert(1, 16658, maxprec, minexp_s)) bit for
+    bit, minexp_s = max(emax_s - rel_bits, -94) (capped for emax_s = 128: include/gcow.h), with no host
+    synchronisation for the maxima. tensors / outs / bits as
+    roundtrip_tensors' (bits: the sum of the per-tensor stream lengths). absmax: optional float32[len(tensors)] device
+    tensor that receives every tensor's largest finite magnitude (0 for empty, all-zero or all-non-finite tensors);
+    without it one is allocated and kept on the plan object (plan.absmax). plan: a TensorListRelative kept by the
+    caller. 0 <= rel_bits <= 24. Returns the list of outputs."""
+    if plan is None:
+        plan = TensorListRelative(rel_bits, maxprec)
+    elif (plan.rel_bits, plan.maxprec) != (int(rel_bits), int(maxprec)):
+        raise GcowError("roundtrip_tensors_relative: the plan object was made for rel_bits %d, maxprec %d"
+                        % (plan.rel_bits, plan.maxprec))
+    return plan(tensors, outs, absmax, bits, stream)
+
+
+def roundtrip_gradients_relative(parameters, rel_bits: int, bits: torch.Tensor | None = None, stream=None,
+                                 cache: dict | None = None, maxprec: int = 64) -> TensorListRelative:
+    """roundtrip_gradients with a tolerance relative to each gradient tensor: p.grad of every parameter that has one,
+    in iteration order, round-tripped in place by roundtrip_tensors_relative. The plan object lives in `cache`
+    (default: codec.gradient_plans) under (rel_bits, maxprec, device). Returns it (stats(), rebuilds, absmax)."""
+    grads = [q.grad for q in parameters if q.grad is not None]
+    if cache is None:
+        cache = gradient_plans
+    dev = grads[0].device if grads else None
+    key = ("relative", int(rel_bits), int(maxprec), str(dev))
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = TensorListRelative(rel_bits, maxprec)
+    plan(grads, None, None, bits, stream)
+    return plan
+
+
 def field_of_shape(shape, dtype) -> ZfpInput:
     f = ZfpInput()
     f.dtype = DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_FLOAT

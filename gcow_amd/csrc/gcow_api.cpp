@@ -1169,6 +1169,183 @@ gcow_status gcow_roundtrip_list_device(const void* h_plan, const void* d_plan, s
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- round trip, relative
+static const size_t kRelHeaderBytes = (sizeof(gcow::RtRelHeader) + 15) / 16 * 16;
+
+size_t gcow_roundtrip_rel_plan_bytes(size_t nsegs, uint64_t total_values)
+{
+  // a tensor's blocks are its own: at most total / 4 + nsegs of them. Every tensor ends at most one direct chunk
+  // short of full and contributes one piece; the gather blocks end one chunk short of full
+  const uint64_t nblocks = total_values / 4 + nsegs;
+  const uint64_t nchunks = nblocks / gcow::kRtListChunkBlocks, ngather = nblocks / gcow::kRtRelGatherBlocks;
+  return kRelHeaderBytes + (size_t)(nchunks + nsegs) * sizeof(gcow::RtRelDirect) +
+         (size_t)(ngather + 1) * sizeof(gcow::RtRelGather) + nsegs * sizeof(gcow::RtRelPiece);
+}
+
+gcow_status gcow_roundtrip_rel_plan(const void* const* in_ptrs, void* const* out_ptrs, const uint64_t* counts,
+                                    size_t nsegs, data_type in_dtype, data_type out_dtype, void* h_plan,
+                                    size_t plan_bytes, size_t* used_bytes)
+{
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan buffer");
+  if (nsegs && (!in_ptrs || !counts)) return fail(GCOW_ERR_INVALID, "null pointer or count array");
+  if (in_dtype != dtype_float && in_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip supports dtype_float and dtype_bf16 fields");
+  if (out_dtype != dtype_float && out_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip writes dtype_float or dtype_bf16");
+  if (!out_ptrs && in_dtype != out_dtype)
+    return fail(GCOW_ERR_INVALID, "in place (out_ptrs NULL) needs equal dtypes");
+  if (nsegs >= (1ull << 32)) return fail(GCOW_ERR_UNSUPPORTED, "more than 2^32 tensors per call");
+  const size_t ei = in_dtype == dtype_bf16 ? 2 : 4, eo = out_dtype == dtype_bf16 ? 2 : 4;
+  uint64_t nvals = 0, nblocks = 0;
+  size_t nlive = 0;
+  for (size_t s = 0; s < nsegs; s++) {
+    if (!counts[s]) continue;
+    const void* ip = in_ptrs[s];
+    const void* op = out_ptrs ? out_ptrs[s] : in_ptrs[s];
+    if (!ip || !op) return fail(GCOW_ERR_INVALID, "null tensor pointer with a non-zero count");
+    if ((uintptr_t)ip % ei || (uintptr_t)op % eo) return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+    if (counts[s] >= (1ull << 34) || nblocks + (counts[s] + 3) / 4 >= (1ull << 32))
+      return fail(GCOW_ERR_UNSUPPORTED, "more than 2^32 blocks per call");
+    nvals += counts[s];
+    nblocks += (counts[s] + 3) / 4;
+    nlive++;
+  }
+  if (plan_bytes < gcow_roundtrip_rel_plan_bytes(nlive, nvals))
+    return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_roundtrip_rel_plan_bytes()");
+  if ((uintptr_t)h_plan % 8) return fail(GCOW_ERR_INVALID, "misaligned plan buffer");
+
+  std::vector<gcow::RtRelDirect> dir;
+  std::vector<gcow::RtRelGather> gat;
+  std::vector<gcow::RtRelPiece> pcs;
+  const uint64_t CB = gcow::kRtListChunkBlocks;
+  uint64_t vb = 0;  // gather blocks so far
+  for (size_t s = 0; s < nsegs; s++) {
+    const uint64_t n = counts[s];
+    if (!n) continue;
+    const uint64_t ia = (uint64_t)(uintptr_t)in_ptrs[s], oa = (uint64_t)(uintptr_t)(out_ptrs ? out_ptrs[s] : in_ptrs[s]);
+    const uint64_t nb = (n + 3) / 4;
+    uint64_t nfull = n / 4;  // the blocks that run direct
+    if (nfull < gcow::kRtRelMinDirectBlocks || ia % 4 || oa % 4) nfull = 0;
+    for (uint64_t b = 0; b < nfull; b += CB)
+      dir.push_back({ia + b * 4 * ei, oa + b * 4 * eo, (uint32_t)std::min(CB, nfull - b), (uint32_t)s});
+    if (nfull < nb) {
+      pcs.push_back({ia, oa, n, (uint32_t)vb, (uint32_t)nfull, (uint32_t)s, 0u});
+      vb += nb - nfull;
+    }
+  }
+  size_t lo = 0;
+  const uint64_t GB = gcow::kRtRelGatherBlocks;
+  for (uint64_t v0 = 0; v0 < vb; v0 += GB) {
+    const uint64_t v1 = std::min(v0 + GB, vb);
+    while (lo + 1 < pcs.size() && pcs[lo + 1].vb <= v0) lo++;
+    size_t hi = lo;
+    while (hi + 1 < pcs.size() && pcs[hi + 1].vb < v1) hi++;
+    gat.push_back({(uint32_t)v0, (uint32_t)(v1 - v0), (uint32_t)lo, (uint32_t)hi});
+  }
+
+  gcow::RtRelHeader H;
+  std::memset(&H, 0, sizeof(H));
+  H.magic = gcow::kRtRelMagic;
+  H.in_dtype = in_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32;
+  H.out_dtype = out_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32;
+  H.nsegs = (uint32_t)nsegs;
+  H.nlive = (uint32_t)nlive;
+  H.ndirect = (uint32_t)dir.size();
+  H.ngather = (uint32_t)gat.size();
+  H.npieces = (uint32_t)pcs.size();
+  H.nvals = nvals;
+  H.nblocks = nblocks;
+  H.off_direct = kRelHeaderBytes;
+  H.off_gather = H.off_direct + dir.size() * sizeof(gcow::RtRelDirect);
+  H.off_pieces = H.off_gather + gat.size() * sizeof(gcow::RtRelGather);
+  H.bytes = H.off_pieces + pcs.size() * sizeof(gcow::RtRelPiece);
+  if (H.bytes > plan_bytes) return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_roundtrip_rel_plan_bytes()");
+  char* base = (char*)h_plan;
+  std::memset(base, 0, kRelHeaderBytes);
+  std::memcpy(base, &H, sizeof(H));
+  if (!dir.empty()) std::memcpy(base + H.off_direct, dir.data(), dir.size() * sizeof(gcow::RtRelDirect));
+  if (!gat.empty()) std::memcpy(base + H.off_gather, gat.data(), gat.size() * sizeof(gcow::RtRelGather));
+  if (!pcs.empty()) std::memcpy(base + H.off_pieces, pcs.data(), pcs.size() * sizeof(gcow::RtRelPiece));
+  if (used_bytes) *used_bytes = (size_t)H.bytes;
+  return GCOW_OK;
+}
+
+// The header of a host plan, checked against the buffer's size
+static gcow_status rel_header(const void* h_plan, size_t plan_bytes, gcow::RtRelHeader& H)
+{
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan");
+  if (plan_bytes < sizeof(H)) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  std::memcpy(&H, h_plan, sizeof(H));
+  if (H.magic != gcow::kRtRelMagic) return fail(GCOW_ERR_INVALID, "not a plan of gcow_roundtrip_rel_plan");
+  if (plan_bytes < H.bytes) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_rel_plan_stats(const void* h_plan, size_t plan_bytes, gcow_roundtrip_rel_stats* stats)
+{
+  gcow::RtRelHeader H;
+  gcow_status st = rel_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!stats) return fail(GCOW_ERR_INVALID, "null stats");
+  stats->total_values = H.nvals;
+  stats->total_blocks = H.nblocks;
+  stats->segments = H.nlive;
+  stats->direct_chunks = H.ndirect;
+  stats->gather_chunks = H.ngather;
+  stats->used_bytes = H.bytes;
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_rel_plan_chunk(const void* h_plan, size_t plan_bytes, int gather, uint64_t i, uint64_t* tensor,
+                                          uint64_t* block0, uint64_t* nblocks)
+{
+  gcow::RtRelHeader H;
+  gcow_status st = rel_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!tensor || !block0 || !nblocks) return fail(GCOW_ERR_INVALID, "null result pointer");
+  const char* base = (const char*)h_plan;
+  if (!gather) {
+    if (i >= H.ndirect) return fail(GCOW_ERR_INVALID, "chunk index out of range");
+    gcow::RtRelDirect d;
+    std::memcpy(&d, base + H.off_direct + i * sizeof(d), sizeof(d));
+    // the chunk's first block in its tensor: the tensor's first chunk is the first descriptor that names it
+    uint64_t first = i;
+    gcow::RtRelDirect f = d;
+    while (first > 0) {
+      gcow::RtRelDirect q;
+      std::memcpy(&q, base + H.off_direct + (first - 1) * sizeof(q), sizeof(q));
+      if (q.seg != d.seg) break;
+      f = q;
+      first--;
+    }
+    *tensor = d.seg, *block0 = (d.in - f.in) / (H.in_dtype == gcow::DT_BF16 ? 8 : 16), *nblocks = d.nb;
+    return GCOW_OK;
+  }
+  if (i >= H.npieces) return fail(GCOW_ERR_INVALID, "piece index out of range");
+  gcow::RtRelPiece p;
+  std::memcpy(&p, base + H.off_pieces + i * sizeof(p), sizeof(p));
+  *tensor = p.seg, *block0 = p.b0, *nblocks = (p.n + 3) / 4 - p.b0;
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_rel_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t rel_bits,
+                                      uint32_t maxprec, float* d_absmax, uint64_t* d_total_bits, void* hip_stream)
+{
+  gcow::RtRelHeader H;
+  gcow_status st = rel_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (rel_bits > gcow::kRtRelMaxBits) return fail(GCOW_ERR_INVALID, "rel_bits above 24");
+  const gcow_params p = {1, 16658, maxprec, gcow::kRtRelMinExpFloor};
+  if ((st = check_params(&p, 1))) return st;
+  if (H.nsegs && !d_absmax) return fail(GCOW_ERR_INVALID, "null d_absmax");
+  if ((uintptr_t)d_absmax % 4) return fail(GCOW_ERR_INVALID, "misaligned d_absmax");
+  if ((uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "misaligned d_total_bits");
+  if (H.nvals && (!d_plan || (uintptr_t)d_plan % 8)) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  if (!H.nsegs && !d_total_bits) return GCOW_OK;  // an empty list and no bit count: nothing to write
+  GCOW_HIP(gcow::launch_roundtrip_rel1d(H, d_plan, rel_bits, maxprec, (uint32_t*)d_absmax, d_total_bits, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

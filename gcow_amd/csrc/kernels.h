@@ -140,6 +140,47 @@ static_assert(sizeof(RtListDirect) == 24 && sizeof(RtListGather) == 16 && sizeof
 // h: the plan's header (HOST copy); d_plan: the whole plan on the DEVICE. total as launch_roundtrip1d's.
 hipError_t launch_roundtrip_list1d(const RtListHeader& h, const void* d_plan, const Params& p, uint64_t* total,
                                    void* stream);
+// Round trip over a tensor list with a tolerance relative to each tensor (roundtrip_rel1d.hip): every tensor is a
+// field of its own, coded with minexp_s = max(emax_s - rel_bits, kRtRelMinExpFloor), emax_s the exponent of the
+// tensor's largest finite magnitude, which a first pass leaves in absmax[seg]. The plan (gcow_roundtrip_rel_plan,
+// gcow_api.cpp) is one buffer: RtRelHeader, then ndirect RtRelDirect, ngather RtRelGather and npieces RtRelPiece.
+// Blocks are each tensor's own. A tensor's whole blocks run direct, in chunks of up to kRtListChunkBlocks, when it has
+// at least kRtRelMinDirectBlocks of them and its rows lie at 4-byte aligned addresses; every other block (the partial
+// last block of any tensor, short tensors, rows off 4 bytes) is a gather block. Gather blocks are numbered through
+// the pieces in list order (virtual blocks) and cut into chunks of kRtRelGatherBlocks: one block per lane, since a gather
+// lane's time is a chain of dependent loads (the bisection, then its values) that only more workgroups shorten.
+constexpr uint32_t kRtRelMagic = 0x4c525267u;  // "gRRL"
+constexpr uint32_t kRtRelMinDirectBlocks = 256;
+constexpr uint32_t kRtRelGatherBlocks = 256;
+constexpr int32_t kRtRelMinExpFloor = -94;  // blocks with emax <= -98 then have precision 0 and decode to +0
+constexpr uint32_t kRtRelMaxBits = 24;
+constexpr int32_t kRtRelHeadroom = 2;  // a maximum in the top binade: minexp <= floor(log2(2^128 - a)) - this (rel_params)
+struct RtRelDirect {  // nb whole blocks of tensor seg (the caller's numbering), rows at 4-byte aligned addresses
+  uint64_t in, out;   // the chunk's first row
+  uint32_t nb, seg;
+};
+struct RtRelGather {  // virtual blocks vb0 .. vb0 + nb - 1, which lie in pieces p_lo .. p_hi
+  uint32_t vb0, nb;
+  uint32_t p_lo, p_hi;
+};
+struct RtRelPiece {  // the gather blocks of one tensor: its blocks b0 .. ceil(n / 4) - 1 are virtual blocks vb ..
+  uint64_t in, out;  // the tensor's first value
+  uint64_t n;        // the tensor's values
+  uint32_t vb, b0;
+  uint32_t seg, pad;
+};
+struct RtRelHeader {
+  uint32_t magic, in_dtype, out_dtype, nsegs;  // nsegs: the caller's list, empty tensors included
+  uint32_t nlive, ndirect, ngather, npieces;
+  uint64_t nvals, nblocks;
+  uint64_t off_direct, off_gather, off_pieces, bytes;  // byte offsets into the plan; bytes = the plan's used size
+};
+static_assert(sizeof(RtRelDirect) == 24 && sizeof(RtRelGather) == 16 && sizeof(RtRelPiece) == 40 &&
+              sizeof(RtRelHeader) == 80, "plan layout");
+// h: the plan's header (HOST copy); d_plan: the whole plan on the DEVICE. absmax: DEVICE, h.nsegs words, written whole.
+// total (optional): set to the sum of every block's bit length.
+hipError_t launch_roundtrip_rel1d(const RtRelHeader& h, const void* d_plan, uint32_t rel_bits, uint32_t maxprec,
+                                  uint32_t* absmax, uint64_t* total, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

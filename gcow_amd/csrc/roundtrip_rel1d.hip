@@ -1,0 +1,278 @@
+// roundtrip_rel1d.hip -- the fused no-budget round trip (roundtrip1d.hip k_roundtrip1d_var) of every tensor of a list
+// as a field of its own, with a tolerance relative to that tensor (gcow_roundtrip_rel_device, include/gcow.h):
+// tensor s is coded under expert(1, 16658, maxprec, minexp_s), minexp_s = max(emax_s - rel_bits, -94), where emax_s is
+// the block-exponent (biased exponent - 126) of the tensor's largest finite magnitude a_s (and, for emax_s = 128 only,
+// minexp_s capped so that the decode stays finite: rel_params). Nothing is synchronised
+// with the host: a first pass leaves a_s in absmax[s] and the round trip kernels read it from there.
+//   k_rel_init       absmax[0 .. nsegs) = 0 and *total = 0, in stream order
+//   k_rel_absmax     one pass over all values, one workgroup per plan chunk. |x| is taken as integer bits with Inf / NaN
+//                    masked to 0, so the unsigned maximum is the maximum magnitude. A direct chunk (one tensor) loads
+//                    its rows as the round trip does (16-byte fp32 rows, 8-byte bf16 rows, zeros past the chunk),
+//                    reduces over the workgroup and issues one atomicMax; a gather chunk reduces per wave where the
+//                    wave's blocks lie in one tensor, else per lane
+//   k_roundtrip_rel_direct   one workgroup per RtRelDirect: rt_var_chunk (roundtrip1d.h) unchanged, its Params built
+//                    once per workgroup from the tensor's slot of absmax (a uniform load, then scalar arithmetic)
+//   k_roundtrip_rel_gather   one workgroup per RtRelGather (kRtRelGatherBlocks = 256 blocks: one per lane, so that the
+//                    dependent loads of the bisection run in as many workgroups as there are): the lane finds its block's
+//                    tensor by bisection, loads its up to four values one by one, pads a partial block
+//                    (encode.c:41-60), reads all before it writes any and writes only real values. A block never
+//                    crosses a tensor. The block function is rt_var_code with the lane's own Params
+// The results are bit for bit those of gcow_roundtrip_device on each tensor under its parameter set.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <stdint.h>
+#include <utility>
+
+#include "field_io.h"
+#include "roundtrip1d.h"
+
+namespace gcow {
+
+static_assert(kRtListChunkBlocks == 256u * GCOW_RT_U, "the plan's chunk is the workgroup's chunk");
+static_assert(kRtRelGatherBlocks <= kRtListChunkBlocks, "a gather chunk fits the workgroup's U rounds");
+
+typedef unsigned int rel_v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int rel_v4u __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t rel_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// |x| as bits, 0 for Inf / NaN
+__device__ __forceinline__ uint32_t rel_mag(uint32_t bits)
+{
+  const uint32_t a = bits & 0x7fffffffu;
+  return a < 0x7f800000u ? a : 0u;
+}
+
+// The tensor's parameter set from its largest finite magnitude (as bits): emax = (a >> 23) - 126, a subnormal or zero
+// maximum gives -126. The floor keeps every block whose values all cast to INT_MIN (emax <= -98) at precision 0.
+// The headroom cap keeps the decode finite: a value decodes to within 2^minexp of itself, so a tensor whose maximum
+// lies in the top binade (emax = 128) needs a + 2^minexp < 2^128, or a finite value near the maximum comes back as
+// Inf. With g = 2^128 - a = (2^24 - mantissa) 2^104 and hexp = floor(log2 g), minexp <= hexp - 2 leaves
+// |decode| <= 2^128 - 3 g / 4, which is below the fp32 rounding boundary 2^128 - 2^103 since g >= 2^104. For
+// emax <= 127, a + 2^minexp < 2^128 holds by itself and the cap is absent.
+__device__ __forceinline__ Params rel_params(uint32_t a, uint32_t rel_bits, uint32_t maxprec)
+{
+  const uint32_t E = a >> 23;
+  int minexp = max((int)E - 126 - (int)rel_bits, kRtRelMinExpFloor);
+  if (E == 254u) {
+    const uint32_t gap = 0x1000000u - ((a & 0x7fffffu) | 0x800000u);  // 1 .. 2^23, in units of 2^104
+    minexp = min(minexp, 104 + (31 - (int)__builtin_clz(gap)) - kRtRelHeadroom);
+  }
+  return Params{1u, 16658u, maxprec, minexp};
+}
+
+__global__ __launch_bounds__(256) void k_rel_init(uint32_t* __restrict__ absmax, uint32_t nsegs, uint64_t* total)
+{
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nsegs; i += gridDim.x * 256u) absmax[i] = 0u;
+  if (total && blockIdx.x == 0 && threadIdx.x == 0) *total = 0ull;
+}
+
+// ------------------------------------------------------------------------------------------------ gather blocks
+// Virtual block vb0 + i of a gather chunk: the last piece that starts at or before it (at most log2(pieces of the
+// chunk) steps), then the block's place in that piece's tensor.
+struct RelBlock {
+  const char* in;
+  char* out;
+  uint64_t x0;  // the block's first value in its tensor
+  uint32_t nv;  // real values, 1 .. 4
+  uint32_t seg;
+};
+
+__device__ __forceinline__ RelBlock rel_locate(const RtRelGather& c, const RtRelPiece* __restrict__ pieces, uint32_t i)
+{
+  const uint32_t v = c.vb0 + i;
+  uint32_t lo = c.p_lo, hi = c.p_hi;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1u) >> 1;
+    if (pieces[mid].vb <= v) lo = mid;
+    else hi = mid - 1u;
+  }
+  const RtRelPiece e = pieces[lo];
+  RelBlock b;
+  b.in = (const char*)e.in;
+  b.out = (char*)e.out;
+  b.x0 = 4ull * ((uint64_t)e.b0 + (v - e.vb));
+  b.nv = (uint32_t)min<uint64_t>(4, e.n - b.x0);
+  b.seg = e.seg;
+  return b;
+}
+
+// ------------------------------------------------------------------------------------------------ the maximum
+// The gather chunks come first in the grid: their lanes chase dependent loads (the bisection), and started last they
+// would run on alone after the direct chunks have drained.
+template <int DT_IN, int U>
+__global__ __launch_bounds__(256) void k_rel_absmax(const RtRelDirect* __restrict__ desc,
+                                                    const RtRelGather* __restrict__ chunks, uint32_t ngather,
+                                                    const RtRelPiece* __restrict__ pieces, uint32_t* absmax)
+{
+  __shared__ uint32_t sh[4];
+  if (blockIdx.x >= ngather) {  // uniform over the workgroup
+    constexpr uint32_t IB = rt_row_bytes<DT_IN>();
+    const RtRelDirect* d = desc + (blockIdx.x - ngather);
+    const uint64_t in = d->in;
+    const uint32_t nb = min(rel_uniform(d->nb), kRtListChunkBlocks), seg = rel_uniform(d->seg);
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(((uint64_t)rel_uniform((uint32_t)(in >> 32)) << 32) | rel_uniform((uint32_t)in)), 0, (int)(nb * IB),
+        0x00020000);
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < U; k++) {  // rows past the chunk read zeros
+      const int off = (int)((threadIdx.x + 256u * k) * IB);
+      if constexpr (DT_IN == DT_BF16) {
+        const rel_v2u v = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, 0);
+        m = max(max(m, rel_mag(v.x << 16)), max(rel_mag(v.x & 0xffff0000u), rel_mag(v.y << 16)));
+        m = max(m, rel_mag(v.y & 0xffff0000u));
+      } else {
+        const rel_v4u v = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0);
+        m = max(max(m, rel_mag(v.x)), max(rel_mag(v.y), max(rel_mag(v.z), rel_mag(v.w))));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t mm = max(max(sh[0], sh[1]), max(sh[2], sh[3]));
+      if (mm) atomicMax(absmax + seg, mm);  // the slot was zeroed: a zero maximum has nothing to add
+    }
+    return;
+  }
+  const RtRelGather c = chunks[blockIdx.x];
+#pragma unroll 1
+  for (int k = 0; k < U && 256u * k < c.nb; k++) {  // c.nb: uniform over the workgroup
+    const uint32_t i = threadIdx.x + 256u * k;
+    uint32_t m = 0, seg = 0;
+    if (i < c.nb) {
+      const RelBlock b = rel_locate(c, pieces, i);
+      seg = b.seg;
+      for (uint32_t x = 0; x < b.nv; x++)
+        m = max(m, rel_mag(__float_as_uint(load_elem<DT_IN>(b.in, (int64_t)(b.x0 + x)))));
+    }
+    // lanes with m = 0 have nothing to add; where the others of the wave share a tensor, one atomic serves them
+    const uint64_t need = __ballot(m != 0u);
+    if (need == 0ull) continue;
+    const uint32_t sref = (uint32_t)__shfl((int)seg, __ffsll((unsigned long long)need) - 1, 64);
+    if (__all(m == 0u || seg == sref)) {
+      uint32_t w = m;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) w = max(w, (uint32_t)__shfl_xor((int)w, o, 64));
+      if ((threadIdx.x & 63u) == 0) atomicMax(absmax + sref, w);
+    } else if (m != 0u) {
+      atomicMax(absmax + seg, m);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ direct chunks
+// Lanes past the chunk's nb blocks read zeros and have their stores dropped by the range check (rt_var_chunk).
+template <int DT_IN, int DT_OUT, bool COUNT, int U>
+__global__ __launch_bounds__(256) void k_roundtrip_rel_direct(const RtRelDirect* __restrict__ desc,
+                                                              const uint32_t* __restrict__ absmax, uint32_t rel_bits,
+                                                              uint32_t maxprec, uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  const RtRelDirect* d = desc + blockIdx.x;
+  const uint64_t in = d->in, out = d->out;
+  const uint32_t ilo = rel_uniform((uint32_t)in), ihi = rel_uniform((uint32_t)(in >> 32));
+  const uint32_t olo = rel_uniform((uint32_t)out), ohi = rel_uniform((uint32_t)(out >> 32));
+  const uint32_t nb = min(rel_uniform(d->nb), kRtListChunkBlocks);
+  pipe_v4i rin;
+  rin.x = (int)ilo;
+  rin.y = (int)(ihi & 0xffffu);               // stride 0
+  rin.z = (int)(nb * rt_row_bytes<DT_IN>());   // num_records: the chunk's rows, in bytes
+  rin.w = 0x00020000;
+  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(((uint64_t)ohi << 32) | olo), 0, (int)(nb * rt_row_bytes<DT_OUT>()), 0x00020000);
+  // the tensor's slot: the descriptor's address is uniform, so is this load's
+  const Params p = rel_params(rel_uniform(absmax[rel_uniform(d->seg)]), rel_bits, maxprec);
+  const uint32_t lsum = rt_var_chunk<DT_IN, DT_OUT, COUNT, U>(rin, rout, threadIdx.x, nb, p);
+  if constexpr (COUNT) rt_count(lsum, cnt_sh, total);
+}
+
+// ------------------------------------------------------------------------------------------------ gather chunks
+// Lanes past the chunk code a zero block and neither load nor store: the block function runs with every lane active.
+template <int DT_IN, int DT_OUT, int U>
+__global__ __launch_bounds__(256) void k_roundtrip_rel_gather(const RtRelGather* __restrict__ chunks,
+                                                              const RtRelPiece* __restrict__ pieces,
+                                                              const uint32_t* __restrict__ absmax, uint32_t rel_bits,
+                                                              uint32_t maxprec, uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  constexpr uint32_t OE = DT_OUT == DT_BF16 ? 2u : 4u;
+  const RtRelGather c = chunks[blockIdx.x];
+  uint32_t lsum = 0;
+#pragma unroll 1
+  for (int k = 0; k < U && 256u * k < c.nb; k++) {  // c.nb: uniform over the workgroup
+    const uint32_t i = threadIdx.x + 256u * k;
+    const bool act = i < c.nb;
+    float f[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
+    char* o = nullptr;
+    uint32_t nv = 0, a = 0;
+    if (act) {
+      const RelBlock b = rel_locate(c, pieces, i);
+      nv = b.nv;
+      a = absmax[b.seg];
+      o = b.out + b.x0 * OE;
+#pragma unroll
+      for (uint32_t x = 0; x < 4u; x++)
+        if (x < nv) f[x] = load_elem<DT_IN>(b.in, (int64_t)(b.x0 + x));
+      // pad_index (field_io.h) written out: 1 -> v0 v0 v0 v0, 2 -> v0 v1 v1 v0, 3 -> v0 v1 v2 v0
+      if (nv < 2u) f[1] = f[0];
+      if (nv < 3u) f[2] = nv == 2u ? f[1] : f[0];
+      if (nv < 4u) f[3] = f[0];
+    }
+    const Params p = rel_params(a, rel_bits, maxprec);
+    const uint32_t len = rt_var_code(f, p, d);
+    lsum += act ? len : 0u;
+#pragma unroll
+    for (uint32_t x = 0; x < 4u; x++)
+      if (x < nv) {
+        if constexpr (DT_OUT == DT_BF16) ((uint16_t*)o)[x] = (uint16_t)bf16_rne(d[x]);
+        else ((float*)o)[x] = d[x];
+      }
+  }
+  if (total) rt_count(lsum, cnt_sh, total);  // total: a kernel argument, uniform over the workgroup
+}
+
+// ------------------------------------------------------------------------------------------------ launchers
+template <int DT_IN, int DT_OUT>
+static void launch_rel_t(const RtRelHeader& h, const char* d_plan, uint32_t rel_bits, uint32_t maxprec,
+                         uint32_t* absmax, uint64_t* total, hipStream_t st)
+{
+  constexpr int U = GCOW_RT_U;
+  const RtRelDirect* dd = (const RtRelDirect*)(d_plan + h.off_direct);
+  const RtRelGather* gg = (const RtRelGather*)(d_plan + h.off_gather);
+  const RtRelPiece* pp = (const RtRelPiece*)(d_plan + h.off_pieces);
+  k_rel_absmax<DT_IN, U><<<h.ngather + h.ndirect, 256, 0, st>>>(dd, gg, h.ngather, pp, absmax);
+  if (h.ndirect) {
+    if (total)
+      k_roundtrip_rel_direct<DT_IN, DT_OUT, true, U><<<h.ndirect, 256, 0, st>>>(dd, absmax, rel_bits, maxprec, total);
+    else
+      k_roundtrip_rel_direct<DT_IN, DT_OUT, false, U><<<h.ndirect, 256, 0, st>>>(dd, absmax, rel_bits, maxprec,
+                                                                                nullptr);
+  }
+  if (h.ngather)
+    k_roundtrip_rel_gather<DT_IN, DT_OUT, U><<<h.ngather, 256, 0, st>>>(gg, pp, absmax, rel_bits, maxprec, total);
+}
+
+hipError_t launch_roundtrip_rel1d(const RtRelHeader& h, const void* d_plan, uint32_t rel_bits, uint32_t maxprec,
+                                  uint32_t* absmax, uint64_t* total, void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  if (h.nsegs || total)
+    k_rel_init<<<std::max(1u, std::min((h.nsegs + 255u) / 256u, 64u)), 256, 0, st>>>(absmax, h.nsegs, total);
+  if (h.ndirect + h.ngather) {
+    const char* dp = (const char*)d_plan;
+    if (h.in_dtype == DT_F32) {
+      if (h.out_dtype == DT_F32) launch_rel_t<DT_F32, DT_F32>(h, dp, rel_bits, maxprec, absmax, total, st);
+      else launch_rel_t<DT_F32, DT_BF16>(h, dp, rel_bits, maxprec, absmax, total, st);
+    } else {
+      if (h.out_dtype == DT_F32) launch_rel_t<DT_BF16, DT_F32>(h, dp, rel_bits, maxprec, absmax, total, st);
+      else launch_rel_t<DT_BF16, DT_BF16>(h, dp, rel_bits, maxprec, absmax, total, st);
+    }
+  }
+  return hipGetLastError();
+}
+
+}  // namespace gcow

@@ -75,7 +75,14 @@ class GcowHookState:
     keeps a second carried error, of its mean shard (keyed by bucket index, "mean" and the shard's numel; cleared by
     reset_error_feedback()). Per rank, n fp32 values at rate 16 then cost 7/8 (2n + 2n) bytes instead of
     7/8 (2n + 4n) at W = 8. The mean is coded from its fp32 values whatever the bucket's dtype: for a bf16 bucket the
-    second stage saves bytes only below 16 bits per value. Unset (the default): nothing changes."""
+    second stage saves bytes only below 16 bits per value. Unset (the default): nothing changes.
+
+    `relative_bits` (roundtrip_hook only; the two wire hooks raise ValueError with it set: their decoder would need the
+    per-tensor exponents on the wire): after the mean all-reduce every parameter's gradient in the bucket
+    (bucket.gradients(), views of the buffer) is round-tripped in place as a field of its own, in accuracy mode under
+    a tolerance of 2^-relative_bits relative to that gradient's largest magnitude (codec.roundtrip_tensors_relative,
+    through the codec's roundtrip_relative, cached per bucket). `params` contributes only its maxprec. The bucket must
+    be fp32 or bf16. Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -88,6 +95,8 @@ class GcowHookState:
     # compressed_sharded_hook: the mean shards travel compressed too (class docstring); the other hooks refuse it
     compress_mean: bool = False
     mean_params: GcowParams | None = None  # the mean's parameter set; None: `params`
+    # roundtrip_hook: a tolerance relative to each parameter's gradient (class docstring); the wire hooks refuse it
+    relative_bits: int | None = None
     _worker: object = field(default=None, repr=False)
     _side: dict = field(default_factory=dict, repr=False)
     _comm_group: object = field(default=None, repr=False)
@@ -209,6 +218,10 @@ def _encode(state: GcowHookState, cdc, bucket, x: torch.Tensor, stride: int, slo
     return cdc.encode_residual(x, state.error_buffer(index, x), state.params, stride, slot=slot)
 
 
+_RELATIVE_WIRE = ("relative_bits is for roundtrip_hook: a stream coded under per-tensor exponents needs them on the "
+                  "wire to be decoded, which the wire hooks do not send")
+
+
 def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
     """Mean all-reduce, then the lossy encode -> decode the reference applies (zfpy), device-resident: one fused
     `roundtrip` call on an fp32 / bf16 bucket when the codec has one, else encode followed by decode."""
@@ -220,12 +233,22 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
                          "roundtrip_hook puts no mean shard on the wire")
     group = state.process_group
     buf = bucket.buffer()
+    cdc = state.get_codec()
+    rel = state.relative_bits
+    if rel is not None:
+        if not hasattr(cdc, "roundtrip_relative"):
+            raise ValueError("relative_bits needs a codec with roundtrip_relative (gcow_amd.dist.DeviceCodec)")
+        if buf.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("relative_bits takes fp32 or bf16 buckets, got %s" % buf.dtype)
     world = dist.get_world_size(group)
     fut = dist.all_reduce(buf.div_(world), group=group, async_op=True).get_future()
-    cdc = state.get_codec()
 
     def lossy(f):
         t = f.value()[0]
+        if rel is not None:  # each parameter's view of the bucket, in place, under its own tolerance
+            cdc.roundtrip_relative(bucket.gradients(), rel, maxprec=state.params.maxprec,
+                                   slot=("rel", bucket.index()))
+            return t
         flat, x = _flat(t)
         if hasattr(cdc, "roundtrip") and flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous():
             cdc.roundtrip(x, state.params, out=flat)  # one kernel, in place, no stream (same bits as the path below)
@@ -300,6 +323,8 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     if state.compress_mean:
         raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
                          "compressed_allgather_hook decodes every rank's stream on every rank and sends no mean")
+    if state.relative_bits is not None:
+        raise ValueError(_RELATIVE_WIRE)
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -398,6 +423,8 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     With state.compress_mean the second stage is compressed too (gcow_amd.dist.allgather_mean_streams): the owner
     codes the mean of its pieces without storing it (cdc.decode_mean_encode; a codec without that method composes
     decode_mean and encode), and the bucket ends as decode(encode(mean)) under state.mean_params on every rank."""
+    if state.relative_bits is not None:
+        raise ValueError(_RELATIVE_WIRE)
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)

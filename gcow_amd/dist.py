@@ -116,6 +116,25 @@ class DeviceCodec:
         from . import codec
         return codec.roundtrip(x, params, out=out)
 
+    def roundtrip_relative(self, tensors, rel_bits: int, maxprec: int = 64, slot=None):
+        """Every tensor of the list round-tripped in place under a tolerance relative to its own largest magnitude
+        (codec.roundtrip_tensors_relative). The plan object (pinned plan, device copy, the maxima) is cached per
+        (slot, rel_bits, maxprec, device) under the encoders' idleness rule, so a list that stays where it is plans
+        once. Returns the tensors."""
+        from . import codec
+        tensors = list(tensors)
+        self._tick += 1
+        dev = tensors[0].device if tensors else None
+        key = (slot, int(rel_bits), int(maxprec), dev, "relative")
+        ent = self._enc.get(key)
+        if ent is None:
+            ent = self._enc[key] = [codec.TensorListRelative(rel_bits, maxprec), self._tick]
+        else:
+            ent[1] = self._tick
+            self._enc.move_to_end(key)
+        self._evict_idle()
+        return ent[0](tensors)
+
     def pack_index16(self, index8, n: int, params):
         from . import codec
         return codec.pack_index16(index8, n, params)

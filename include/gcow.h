@@ -376,6 +376,72 @@ gcow_status gcow_roundtrip_list_device(const void* h_plan, const void* d_plan, s
                                        const gcow_params* p, uint64_t* d_total_bits, void* hip_stream);
 
 /*
+ * Round trip over a tensor list with a tolerance relative to each tensor. Every tensor t_s (n_s values) is a 1-D field
+ * of its own, coded in accuracy mode under a tolerance that follows its largest magnitude, found on the device:
+ *   a_s      = the largest |t_s[i]| over the finite values; +0 if there is none (empty, all zero, all NaN / Inf)
+ *   emax_s   = (bits(a_s) >> 23) - 126, the codec's block-exponent convention (a subnormal or zero maximum: -126)
+ *   minexp_s = max(emax_s - rel_bits, -94); for emax_s = 128 only, min(that, floor(log2(2^128 - a_s)) - 2)
+ *   p_s      = expert(minbits 1, maxbits 16658, maxprec, minexp_s)
+ *   out_s    = exactly what gcow_roundtrip_device(field(t_s), p_s, out_s, out_dtype, ...) writes: blocks are the
+ *              tensor's own, counted from its first value, its last block padded as a partial block; only real values
+ *              are written and nothing outside [out_s, out_s + n_s)
+ *   d_absmax[s] = a_s as fp32 for every s of the caller's numbering (empty tensors: 0)
+ *   *d_total_bits = the sum over s of the bit length gcow_encode_device(t_s, p_s) would report
+ * Bound: |out - t| <= 2^minexp_s, below 2^(1 - rel_bits) max|t_s| where the floor is inactive, and every finite block
+ * decodes to finite values. 0 <= rel_bits <= 24 (the bound fails once the 32-plane cap binds). Neither clamp is
+ * cosmetic. The floor of -94: blocks with emax <= -98 cast every value to INT_MIN (the reference's x86 cast), and without
+ * it a tensor of scale 1e-40 would decode to garbage of twice its magnitude; with it every such block has precision 0 and
+ * decodes to +0. The cap for a maximum in the top binade: a value decodes to within 2^minexp_s of itself, so without
+ * it a tensor of scale 3e38 at rel_bits 0 (4 planes, minexp_s = 128) decodes finite values of 2.4e38 and more to Inf.
+ * With g = 2^128 - a_s >= 2^104, minexp_s <= floor(log2 g) - 2 keeps |out| <= 2^128 - 3 g / 4, below the point where
+ * fp32 rounds to Inf. It costs a few more planes for such tensors only (at most rel_bits 26 in effect).
+ * All inputs share in_dtype and all outputs out_dtype (dtype_float or dtype_bf16, in any combination; bf16 input is
+ * widened exactly). out_s == in_s is allowed when the dtypes are equal; any other overlap is undefined.
+ *
+ * As for the list form the address arithmetic is a host PLAN of private layout; it depends on neither rel_bits nor
+ * maxprec, which are arguments of the device call only:
+ *   gcow_roundtrip_rel_plan_bytes(nsegs, total_values): an upper bound of the plan's size.
+ *   gcow_roundtrip_rel_plan: fills the caller's HOST buffer h_plan (8-byte aligned). Arguments as
+ *     gcow_roundtrip_list_plan's. A tensor's whole blocks run DIRECT, in chunks of up to 2048 blocks (one workgroup,
+ *     gcow_roundtrip_device's block sequence), when it has at least 256 of them and its input and output lie at
+ *     4-byte aligned addresses. Every other block is a GATHER block: the partial last block of any tensor, tensors
+ *     of fewer than 256 whole blocks, bf16 tensors at an odd element offset. Gather blocks are numbered through the
+ *     tensors in list order and cut into chunks of 256, one block per lane; a lane finds its block's tensor by
+ *     bisection and loads its values one by one. No block crosses a tensor.
+ *   gcow_roundtrip_rel_plan_stats: what a plan holds.
+ *   gcow_roundtrip_rel_plan_chunk: TEST / MEASUREMENT ONLY: gather = 0: direct chunk i covers blocks *block0 ..
+ *     *block0 + *nblocks - 1 of tensor *tensor (the caller's numbering); gather != 0: gather piece i (one per tensor
+ *     that has gather blocks, i < the number of such tensors; GCOW_ERR_INVALID past it) likewise.
+ *   gcow_roundtrip_rel_device: the launches -- d_absmax zeroed in stream order, one pass that takes every tensor's
+ *     maximum (|x| as integer bits, non-finite values masked to 0, one atomic per workgroup and tensor), then the
+ *     round trip kernels, which read minexp_s's source from d_absmax. d_absmax: DEVICE float[nsegs], required when
+ *     nsegs > 0, 4-byte aligned; it doubles as the workspace. d_total_bits: optional DEVICE uint64. h_plan / d_plan /
+ *     plan_bytes as gcow_roundtrip_list_device's. Asynchronous on hip_stream: no allocation, no host synchronisation.
+ *     An empty list returns GCOW_OK and writes *d_total_bits = 0.
+ * GCOW_ERR_UNSUPPORTED: a dtype other than float / bf16; 2^32 blocks or more. GCOW_ERR_INVALID: NULL h_plan; a NULL or
+ * misaligned (for its element type) pointer with a non-zero count; out_ptrs NULL with unequal dtypes; plan_bytes too
+ * small; rel_bits > 24; maxprec as check_params has it; NULL d_absmax with nsegs > 0; misaligned d_absmax, d_plan or
+ * d_total_bits.
+ */
+typedef struct {
+  uint64_t total_values;
+  uint64_t total_blocks;  /* the sum of ceil(n_s / 4) */
+  uint64_t segments;      /* non-empty tensors */
+  uint64_t direct_chunks;
+  uint64_t gather_chunks;
+  uint64_t used_bytes;    /* the plan's size */
+} gcow_roundtrip_rel_stats;
+size_t gcow_roundtrip_rel_plan_bytes(size_t nsegs, uint64_t total_values);
+gcow_status gcow_roundtrip_rel_plan(const void* const* in_ptrs, void* const* out_ptrs, const uint64_t* counts,
+                                    size_t nsegs, data_type in_dtype, data_type out_dtype, void* h_plan,
+                                    size_t plan_bytes, size_t* used_bytes);
+gcow_status gcow_roundtrip_rel_plan_stats(const void* h_plan, size_t plan_bytes, gcow_roundtrip_rel_stats* stats);
+gcow_status gcow_roundtrip_rel_plan_chunk(const void* h_plan, size_t plan_bytes, int gather, uint64_t i,
+                                          uint64_t* tensor, uint64_t* block0, uint64_t* nblocks);
+gcow_status gcow_roundtrip_rel_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t rel_bits,
+                                      uint32_t maxprec, float* d_absmax, uint64_t* d_total_bits, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by

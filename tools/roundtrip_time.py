@@ -20,7 +20,12 @@ scalar tensor put first -- every later row of the field then lies off 16-byte al
 single_*: B on one tensor of the same total against plain codec.roundtrip in place on it, the price of the chunk
 descriptors. Each line reports the plan's direct / gather chunk counts. not_slower_*: B is not slower than the faster A
 run by more than A's own run-to-run spread.
-usage: roundtrip_time.py --list [--only NAME]"""
+usage: roundtrip_time.py --list [--only NAME]
+
+--relative: the tolerance relative to each tensor (codec.roundtrip_tensors_relative -> gcow_roundtrip_rel_device,
+rel_bits 8) next to roundtrip_tensors at accuracy 1e-3, in place on the same ResNet-50-shaped list, fp32 and bf16
+(relative_leg's docstring).
+usage: roundtrip_time.py --relative [--only NAME]"""
 import json
 import math
 import os
@@ -166,8 +171,66 @@ def list_leg():
             del ts, bound, flat
 
 
+def relative_leg():
+    """roundtrip_tensors_relative (rel_bits 8) next to roundtrip_tensors at accuracy 1e-3, both in place with a kept
+    plan on clones of the same ResNet-50-shaped list, fp32 and bf16: absolute, relative, absolute again, cold and
+    steady as above. Each tensor of the list is scaled by its own power of two (2^-12 .. 2^0 in module order), the
+    spread of magnitudes the relative form is for. The relative call reads every value twice (the maximum pass)."""
+    shapes = resnet50_shapes()
+    total = sum(math.prod(s) for s in shapes)
+    src = torch.empty(total, dtype=torch.float32, device="cuda")
+    codec.fill_normal(src, 1e-3, seed=0x67636F77, inject=False)
+    offs = [0]
+    for s in shapes:
+        offs.append(offs[-1] + math.prod(s))
+    p = codec.accuracy(1e-3)
+    for dname, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        name = "relative_resnet50_%s_k8" % dname
+        if only and name != only:
+            continue
+
+        def fresh():
+            return [(src[offs[i]:offs[i + 1]] * 2.0 ** -(i % 13)).to(dtype).view(s) for i, s in enumerate(shapes)]
+
+        ta, tr = fresh(), fresh()
+        bits_a = torch.zeros(1, dtype=torch.int64, device="cuda")
+        bits_r = torch.zeros(1, dtype=torch.int64, device="cuda")
+        plan_a = codec.TensorListRoundtrip(p)
+        plan_r = codec.TensorListRelative(8)
+
+        def a_fn():
+            codec.roundtrip_tensors(ta, p, bits=bits_a, stream=st, plan=plan_a)
+
+        def r_fn():
+            codec.roundtrip_tensors_relative(tr, 8, bits=bits_r, stream=st, plan=plan_r)
+
+        a_fn()
+        r_fn()
+        torch.cuda.synchronize()
+        sa, sr = plan_a.stats(), plan_r.stats()
+        res = {"config": name, "tensors": len(shapes), "n": total,
+               "bits_per_value_absolute": round(int(bits_a.item()) / total, 3),
+               "bits_per_value_relative": round(int(bits_r.item()) / total, 3),
+               "absolute_direct_chunks": int(sa.direct_chunks), "absolute_gather_chunks": int(sa.gather_chunks),
+               "relative_direct_chunks": int(sr.direct_chunks), "relative_gather_chunks": int(sr.gather_chunks),
+               "relative_total_blocks": int(sr.total_blocks), "relative_plan_bytes": int(sr.used_bytes)}
+        a1 = cold_and_steady(a_fn)
+        r = cold_and_steady(r_fn)
+        a2 = cold_and_steady(a_fn)
+        for k, i in (("cold", 0), ("steady", 1)):
+            res["relative_%s_ms" % k] = round(r[i], 4)
+            res["absolute_%s_ms" % k] = [round(a1[i], 4), round(a2[i], 4)]
+            res["relative_over_absolute_%s" % k] = round(r[i] / min(a1[i], a2[i]), 3)
+        res["plan_rebuilds"] = [plan_a.rebuilds, plan_r.rebuilds]
+        print(json.dumps(res), flush=True)
+        del ta, tr
+
+
 if "--list" in sys.argv:
     list_leg()
+    sys.exit(0)
+if "--relative" in sys.argv:
+    relative_leg()
     sys.exit(0)
 
 x32 = torch.empty(n, dtype=torch.float32, device="cuda")
