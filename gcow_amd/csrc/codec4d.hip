@@ -202,9 +202,13 @@ __global__ __launch_bounds__(64) void k_encode4d(FieldDesc F, Params p, uint32_t
   const uint64_t base = rbase ? rbase[b] : (uint64_t)b * p.maxbits;
   const uint32_t W = (o0 + total + 31) >> 5;
   const uint64_t gw0 = base >> 5;
+  // a block's first word holds the end of the block before it (or, for block 0 of an appended chunk, of the stream
+  // before the chunk) and its last word the start of the next one: the scan zeroed those (the memset, at fixed rate).
+  // The last block's last word is shared with nobody and nobody zeroed it: it is stored.
+  const bool tail_shared = ((o0 + total) & 31) != 0 && b != F.nblocks - 1;
   for (uint32_t j = lane; j < W; j += 64) {
     const uint32_t v = obuf[j];
-    if ((j == 0 && o0) || (j == W - 1 && ((o0 + total) & 31))) atomicOr(out32 + gw0 + j, v);  // shared words
+    if ((j == 0 && o0) || (j == W - 1 && tail_shared)) atomicOr(out32 + gw0 + j, v);  // shared words
     else out32[gw0 + j] = v;
   }
   if (index && lane == 0 && (b & ((1u << index_shift) - 1)) == 0) index[b >> index_shift] = base;

@@ -150,11 +150,18 @@ gcow_status encode_impl(const zfp_input* field, const gcow_params* p, void* d_ou
                         uint32_t index_stride, void* stream, const uint64_t* d_base = nullptr)
 {
   gcow::FieldDesc F;
-  gcow_status st = make_field(field, F, false);
-  if (st) return st;
+  gcow_status st = GCOW_OK;
+  if (d_base && field && !field->nx && !field->ny && !field->nz && !field->nw) {
+    // an appended chunk without values: zfp_input cannot say "no rows of an N-D field", so it is the field without
+    // extents. No blocks (the F.nblocks == 0 branch below), every other argument checked as for any chunk.
+    std::memset(&F, 0, sizeof(F));
+    F.dims = 1;
+  } else if ((st = make_field(field, F, false))) {
+    return st;
+  }
   if ((st = check_params(p, F.dims))) return st;
   if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
-  const size_t bound = gcow_max_output_bytes(field, p);
+  const size_t bound = F.nblocks ? gcow_max_output_bytes(field, p) : 0;
   if (out_capacity < bound) return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_max_output_bytes()");
   uint32_t shift = 0;
   if (d_index) {
@@ -167,8 +174,9 @@ gcow_status encode_impl(const zfp_input* field, const gcow_params* p, void* d_ou
                                       "offset the output pointer by nblocks * maxbits / 8 on the host)");
   if (F.nblocks == 0) {
     if (d_total_bits) {
-      if (d_base) GCOW_HIP(hipMemcpyAsync(d_total_bits, d_base, 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      else GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, stream));
+      if (!d_base) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, stream));
+      else if (d_total_bits != d_base)
+        GCOW_HIP(hipMemcpyAsync(d_total_bits, d_base, 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     return GCOW_OK;
   }
@@ -186,7 +194,7 @@ gcow_status encode_impl(const zfp_input* field, const gcow_params* p, void* d_ou
     uint64_t* base = sums + F.nblocks;
     uint32_t* lens = (uint32_t*)(base + F.nblocks + 1);
     GCOW_HIP(gcow::launch_encode4d(F, pp, lens, nullptr, nullptr, nullptr, 0, stream));
-    GCOW_HIP(gcow::launch_scan_blocks(lens, F.nblocks, sums, base, d_total_bits, (uint32_t*)d_out, stream));
+    GCOW_HIP(gcow::launch_scan_blocks(lens, F.nblocks, sums, base, d_total_bits, (uint32_t*)d_out, d_base, stream));
     GCOW_HIP(gcow::launch_encode4d(F, pp, nullptr, base, (uint32_t*)d_out, d_index, shift, stream));
     return GCOW_OK;
   }

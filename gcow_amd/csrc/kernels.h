@@ -59,7 +59,7 @@ hipError_t launch_decode4d(const FieldDesc& F, const Params& p, const uint64_t* 
 hipError_t launch_decode4d_seq(const FieldDesc& F, const Params& p, const uint64_t* in, uint64_t base_bits,
                                uint64_t* end, void* stream);
 hipError_t launch_scan_blocks(const uint32_t* lens, uint32_t nblocks, uint64_t* sums, uint64_t* base, uint64_t* total,
-                              uint32_t* out32, void* stream);
+                              uint32_t* out32, const uint64_t* d_base, void* stream);
 // 2-D / 3-D tiles (gcow_blocks.hip); launch_encode_tiles forwards d >= 2 here
 hipError_t launch_encode_tiles23(const FieldDesc& F, const Params& p, const TilePlan& plan, uint32_t* out32,
                                  uint64_t* ws_sums, uint64_t* ws_base, uint64_t* d_total, uint64_t* index,

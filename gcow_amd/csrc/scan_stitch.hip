@@ -24,7 +24,9 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x)
 // Exclusive scan of the range totals (one workgroup). base[] gets nranges + 1 entries (last = total bits); the
 // 32-bit words two ranges share are zeroed so both sides can atomicOr into them; the stream's flush word too.
 // d_base (optional): the stream already holds *d_base bits (chunked / appended encode); every offset starts there and
-// the first range ORs its first word into the bits before it.
+// the first range ORs its first word into the bits before it. Where *d_base lies inside a 32-bit word, that word holds
+// the end of the earlier stream (zero above it) and is never zeroed here, not even for a later range that starts in it
+// (4-D: a range is one block, and a block can be a single bit).
 // One workgroup: the range totals are read in coalesced chunks of 8192 through LDS (each thread then scans 8
 // consecutive totals; wave prefix by shuffles, 16 wave totals through LDS), so every global access is coalesced --
 // a per-thread walk over its own contiguous slice touched 64 cache lines per wave load (82 us at 32 Ki ranges).
@@ -36,7 +38,9 @@ __global__ __launch_bounds__(1024) void k_scan_ranges(const uint64_t* __restrict
   __shared__ uint64_t v[C];
   __shared__ uint64_t wsum[T / 64];
   const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-  uint64_t carry = d_base ? *d_base : 0ull;
+  const uint64_t base0 = d_base ? *d_base : 0ull;
+  const uint64_t keep = (base0 & 31) ? base0 >> 5 : ~0ull;  // the word of the earlier stream's end, if it is partial
+  uint64_t carry = base0;
   for (uint32_t c0 = 0; c0 < nranges; c0 += C) {
     const uint32_t n = min(C, nranges - c0);
 #pragma unroll
@@ -74,7 +78,8 @@ __global__ __launch_bounds__(1024) void k_scan_ranges(const uint64_t* __restrict
       if (j < n) {
         const uint64_t b = v[j];
         base[c0 + j] = b;
-        if (c0 + j > 0 && (b & 31)) out32[b >> 5] = 0u;  // a word two ranges share: zeroed for their atomicOr
+        // a word two ranges share: zeroed for their atomicOr
+        if (c0 + j > 0 && (b & 31) && (b >> 5) != keep) out32[b >> 5] = 0u;
       }
     }
     carry += chunk;
@@ -139,7 +144,9 @@ __global__ __launch_bounds__(256) void k_scan_ranges_mw(const uint64_t* __restri
   if (lane == 63) wsum[wv] = incl;
   if (lane == 0) wpre[wv] = pre;
   __syncthreads();
-  uint64_t before = 0, chunk = 0, carry = d_base ? *d_base : 0ull;
+  const uint64_t base0 = d_base ? *d_base : 0ull;
+  const uint64_t keep = (base0 & 31) ? base0 >> 5 : ~0ull;  // as in k_scan_ranges
+  uint64_t before = 0, chunk = 0, carry = base0;
 #pragma unroll
   for (uint32_t w = 0; w < T / 64; w++) {
     before += w < wv ? wsum[w] : 0ull;
@@ -159,7 +166,7 @@ __global__ __launch_bounds__(256) void k_scan_ranges_mw(const uint64_t* __restri
     if (j < n) {
       const uint64_t b = v[j];
       base[c0 + j] = b;
-      if (c0 + j > 0 && (b & 31)) out32[b >> 5] = 0u;
+      if (c0 + j > 0 && (b & 31) && (b >> 5) != keep) out32[b >> 5] = 0u;
     }
   }
   if (blockIdx.x == gridDim.x - 1 && t == 0) {
@@ -177,8 +184,6 @@ static void scan_ranges(const uint64_t* sums, uint32_t nranges, uint64_t* base, 
     k_scan_ranges<<<1, 1024, 0, st>>>(sums, nranges, base, total, out32, d_base);
 }
 
-// exclusive scan of per-block lengths: one "range" per block through k_scan_ranges (which also zeroes the words
-// two blocks share)
 __global__ void k_widen_u32(const uint32_t* __restrict__ a, uint32_t n, uint64_t* __restrict__ o)
 {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -308,11 +313,13 @@ __global__ __launch_bounds__(256) void k_index_pack16(const uint64_t* __restrict
 // ------------------------------------------------------------------------------------------------ launchers
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
+// exclusive scan of per-block lengths: one "range" per block through k_scan_ranges (which also zeroes the words
+// two blocks share); d_base as there (the 4-D appended encode)
 hipError_t launch_scan_blocks(const uint32_t* lens, uint32_t nblocks, uint64_t* sums, uint64_t* base, uint64_t* total,
-                              uint32_t* out32, void* stream)
+                              uint32_t* out32, const uint64_t* d_base, void* stream)
 {
   k_widen_u32<<<(nblocks + 255) / 256, 256, 0, S(stream)>>>(lens, nblocks, sums);
-  scan_ranges(sums, nblocks, base, total, out32, nullptr, S(stream));
+  scan_ranges(sums, nblocks, base, total, out32, d_base, S(stream));
   return hipGetLastError();
 }
 

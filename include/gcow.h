@@ -230,6 +230,12 @@ gcow_status gcow_encode_device(const zfp_input* field, const gcow_params* p, voi
  * the previous bits plus gcow_max_output_bytes(field, p) (only the latter is checked against out_capacity). Block
  * index entries (d_index) are absolute stream offsets. Fixed-rate streams are chunked by offsetting d_out on the
  * host instead (GCOW_ERR_UNSUPPORTED here).
+ * Every variable-rate field appends, 1-D to 4-D: the 4-D encoder's block scan starts at *d_base_bits like the range
+ * scans of the others, and the chunk's first block ORs its first word into the bits before it. As with
+ * gcow_encode_device, d_out past the previous bits, the workspace and the index need no zeroing: the chunk's flushed
+ * words are written whole, apart from the bits of the word that *d_base_bits falls in, which are kept (the call
+ * before left the rest of that word zero). A chunk without values is the field without extents (nx = ny = nz = nw =
+ * 0; zfp_input cannot say "no rows of an N-D field"): it writes nothing but *d_total_bits = *d_base_bits.
  */
 gcow_status gcow_encode_device_append(const zfp_input* field, const gcow_params* p, void* d_out, size_t out_capacity,
                                       const uint64_t* d_base_bits, uint64_t* d_total_bits, void* d_workspace,
