@@ -130,6 +130,9 @@ def load():
         "gcow_roundtrip_rel_plan_stats": (i32, [vp, sz, P(RoundtripRelStats)]),
         "gcow_roundtrip_rel_plan_chunk": (i32, [vp, sz, i32, u64, P(u64), P(u64), P(u64)]),
         "gcow_roundtrip_rel_device": (i32, [vp, vp, sz, u32, u32, vp, vp, vp]),
+        "gcow_rate_table_workspace_bytes": (sz, [pi]),
+        "gcow_rate_table_device": (i32, [pi, u32, vp, vp, sz, vp]),
+        "gcow_rate_table_fit": (i32, [P(u64), u64, P(i32), P(u64)]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),

@@ -569,6 +569,90 @@ def decode(enc_or_words, shape=None, params: GcowParams | None = None, index: to
     return out
 
 
+# ------------------------------------------------------------------------------------------- accuracy under a budget
+RATE_TABLE_MINEXP_LO, RATE_TABLE_ENTRIES = -154, 288  # include/gcow.h GCOW_RATE_TABLE_*
+RATE_TABLE_TILE_VALUES = 4096  # values one workgroup covers per iteration (csrc/kernels.h kRateTableTileValues)
+
+
+def is_nobudget(p: GcowParams) -> bool:
+    """A variable-rate set whose budget truncates no 1-D block (accuracy, precision, expert(<= 1, >= 160, ...)): the
+    domain the rate table describes."""
+    return p.minbits <= 1 and p.maxbits >= 160
+
+
+class RateTable:
+    """Preallocated rate table (gcow_rate_table_device) for 1-D buckets of n values: calling it with x returns the
+    int64[288] device tensor `table` with table[t] = the bit count codec.encode(x, expert(1, 16658, maxprec,
+    -154 + t)) reports -- for every t from one pass over x, exact. The range is complete (a smaller minexp than -154
+    changes nothing, from 132 on every block is one bit) and the table is non-increasing. No host synchronisation;
+    the table and the workspace are allocated once and need no zeroing."""
+
+    def __init__(self, n: int, dtype, device=None):
+        self.L = load()
+        self.n, self.dtype = int(n), dtype
+        self.device = torch.device(device or "cuda")
+        f = field_of_shape((self.n,), dtype)
+        self.ws_bytes = self.L.gcow_rate_table_workspace_bytes(C.byref(f))
+        self.ws = torch.empty(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
+        self.table = torch.empty(RATE_TABLE_ENTRIES, dtype=torch.int64, device=self.device)
+
+    def __call__(self, x: torch.Tensor, maxprec: int = 64, stream=None) -> torch.Tensor:
+        if x.dim() != 1 or x.numel() != self.n or x.dtype != self.dtype:
+            raise GcowError("RateTable built for %d %s values, got %s %s" % (self.n, self.dtype, tuple(x.shape),
+                                                                            x.dtype))
+        if not (x.is_cuda and x.is_contiguous()):
+            raise GcowError("rate_table expects a contiguous 1-D device tensor")
+        f = field_of(x) if self.n else field_of_shape((0,), self.dtype)
+        check(self.L.gcow_rate_table_device(C.byref(f), int(maxprec), self.table.data_ptr(), self.ws.data_ptr(),
+                                            self.ws_bytes, _stream_ptr(stream)), "gcow_rate_table_device")
+        return self.table
+
+
+def rate_table(x: torch.Tensor, maxprec: int = 64, stream=None) -> torch.Tensor:
+    """One-shot RateTable: the int64[288] device tensor of stream lengths of the 1-D device tensor x (fp32 / bf16)
+    under expert(1, 16658, maxprec, minexp), minexp = -154 .. 133."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("dtype %s not supported (float32, bfloat16)" % x.dtype)
+    return RateTable(x.numel(), x.dtype, x.device)(x, maxprec, stream)
+
+
+def fit_minexp(table, budget_bits: int):
+    """gcow_rate_table_fit: -> (minexp, bits), the smallest minexp of the table whose stream length is <= budget_bits
+    and that length. Host code: a device tensor is copied once (288 int64, 2.3 KB) -- the only synchronisation of the
+    feature; a host tensor, array or list is read as is. GcowError when the budget is below the last entry (one bit
+    per block)."""
+    if isinstance(table, torch.Tensor):
+        table = table.detach().reshape(-1).cpu().tolist()
+    vals = [int(v) for v in table]
+    if len(vals) != RATE_TABLE_ENTRIES:
+        raise GcowError("fit_minexp: a rate table has %d entries, got %d" % (RATE_TABLE_ENTRIES, len(vals)))
+    h = (C.c_uint64 * RATE_TABLE_ENTRIES)(*vals)
+    me, bits = C.c_int(0), C.c_uint64(0)
+    check(load().gcow_rate_table_fit(h, max(int(budget_bits), 0), C.byref(me), C.byref(bits)), "gcow_rate_table_fit")
+    return int(me.value), int(bits.value)
+
+
+def fitted_params(maxprec: int, minexp: int) -> GcowParams:
+    """The parameter set a fit stands for: accuracy mode (no bit budget) at that minexp."""
+    return GcowParams(ZFP_MIN_BITS, ZFP_MAX_BITS, int(maxprec), int(minexp))
+
+
+def fit_accuracy(x: torch.Tensor, bits_per_value: float, maxprec: int = 64, stream=None) -> GcowParams:
+    """The finest accuracy-mode set whose stream of x (1-D device tensor) takes at most floor(bits_per_value * n) bits:
+    expert(1, 16658, maxprec, minexp) with minexp fitted on x's rate table. One pass over x and one 2.3 KB host read,
+    where re-encoding until the length fits costs a full encode and a host read per try."""
+    budget = int(math.floor(bits_per_value * x.numel()))
+    me, _ = fit_minexp(rate_table(x.reshape(-1), maxprec, stream), budget)
+    return fitted_params(maxprec, me)
+
+
+def encode_fitted(x: torch.Tensor, bits_per_value: float, maxprec: int = 64, index_stride: int = 0, stream=None):
+    """-> (Encoded, params): x (1-D device tensor) encoded under fit_accuracy(x, bits_per_value, maxprec). Guarantees
+    Encoded.bits <= floor(bits_per_value * n): the table entry is the encoder's own bit count."""
+    p = fit_accuracy(x, bits_per_value, maxprec, stream)
+    return encode(x, p, index_stride, stream), p
+
+
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):
     """OR src_bits bits of src into dst at dst_bit_offset (device words; dst zeroed beyond earlier content)."""
     L = load()

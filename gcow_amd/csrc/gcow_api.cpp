@@ -982,6 +982,53 @@ gcow_status gcow_roundtrip_device(const zfp_input* field, const gcow_params* p, 
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- rate table
+static_assert(GCOW_RATE_TABLE_MINEXP_LO == gcow::kRateTableMinExpLo &&
+              GCOW_RATE_TABLE_ENTRIES == gcow::kRateTableEntries, "gcow.h and kernels.h agree");
+
+size_t gcow_rate_table_workspace_bytes(const zfp_input* field)
+{
+  (void)field;  // the two 288-bin arrays, whatever the field
+  return gcow::rate_table_workspace_bytes();
+}
+
+gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uint64_t* d_table, void* d_workspace,
+                                   size_t workspace_bytes, void* hip_stream)
+{
+  if (!field) return fail(GCOW_ERR_INVALID, "null field");
+  if (field->ny || field->nz || field->nw) return fail(GCOW_ERR_INVALID, "rate_table takes 1-D fields");
+  if (field->sx != 0 && field->sx != 1) return fail(GCOW_ERR_INVALID, "rate_table takes contiguous fields");
+  if (field->dtype != dtype_float && field->dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "rate_table supports dtype_float and dtype_bf16 fields");
+  if (!d_table || (uintptr_t)d_table % 8) return fail(GCOW_ERR_INVALID, "null or misaligned table");
+  if (!d_workspace || (uintptr_t)d_workspace % 8 || workspace_bytes < gcow::rate_table_workspace_bytes())
+    return fail(GCOW_ERR_INVALID, "workspace null, misaligned or smaller than gcow_rate_table_workspace_bytes()");
+  if (field->nx == 0) {
+    GCOW_HIP(hipMemsetAsync(d_table, 0, GCOW_RATE_TABLE_ENTRIES * sizeof(uint64_t), (hipStream_t)hip_stream));
+    return GCOW_OK;
+  }
+  if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
+  if ((uintptr_t)field->data % (field->dtype == dtype_bf16 ? 2 : 4))
+    return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+  gcow::FieldDesc F;
+  gcow_status st = make_field(field, F, false);
+  if (st) return st;
+  GCOW_HIP(gcow::launch_rate_table1d(F, maxprec, d_table, (uint64_t*)d_workspace, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, int* minexp, uint64_t* bits)
+{
+  if (!h_table || !minexp || !bits) return fail(GCOW_ERR_INVALID, "null argument");
+  for (int t = 0; t < GCOW_RATE_TABLE_ENTRIES; t++)
+    if (h_table[t] <= budget_bits) {
+      *minexp = GCOW_RATE_TABLE_MINEXP_LO + t;
+      *bits = h_table[t];
+      return GCOW_OK;
+    }
+  return fail(GCOW_ERR_INVALID, "budget below one bit per block: no accuracy-mode stream is that short");
+}
+
 // ---------------------------------------------------------------------------------------------- round trip, tensor list
 // Rows of a direct chunk must start at a multiple of this many bytes: 4 (multi-dword buffer accesses are dword-aligned),
 // for either element type. GCOW_RTL_NATURAL_ROWS builds the fallback rule instead: the row's own size, 16 bytes (fp32)

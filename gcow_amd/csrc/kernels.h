@@ -181,6 +181,15 @@ static_assert(sizeof(RtRelDirect) == 24 && sizeof(RtRelGather) == 16 && sizeof(R
 // total (optional): set to the sum of every block's bit length.
 hipError_t launch_roundtrip_rel1d(const RtRelHeader& h, const void* d_plan, uint32_t rel_bits, uint32_t maxprec,
                                   uint32_t* absmax, uint64_t* total, void* stream);
+// Rate table (rate_table1d.hip): table[t], t < kRateTableEntries, = the stream length of the contiguous 1-D field F
+// (fp32 / bf16, any element-aligned address) under expert(1, 16658, maxprec, kRateTableMinExpLo + t), i.e. what
+// launch_encode1d_var_tile leaves in *d_total. ws: rate_table_workspace_bytes(), 8-byte aligned; neither ws nor table
+// needs zeroing. A workgroup covers kRateTableTileValues values per iteration of its grid-stride loop.
+constexpr int32_t kRateTableMinExpLo = -154;
+constexpr uint32_t kRateTableEntries = 288;
+constexpr uint32_t kRateTableTileValues = 4096;
+size_t rate_table_workspace_bytes();
+hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

@@ -1,0 +1,229 @@
+// rate_table1d.hip -- the rate table of a 1-D field (gcow_rate_table_device): table[t], t = 0 .. 287,
+// is the stream length of the field under expert(1, 16658, maxprec, -154 + t), for all t from one pass over the input.
+//
+// A block's coefficients do not depend on minexp (the cast scales by the block's own exponent), and in the no-budget
+// domain its code length is a closed form of the leading planes of the suffix ORs of its four coefficients (v1_prep,
+// var1d_prep.h). With a = emax + 158 the block's precision at entry t is P = min(pmax, max(0, a - t)),
+// pmax = min(maxprec, 32), and its length is L(0) = 1,
+//   L(P) = 13 + 4 (P - 1) - sum_{j<3} min(z_j, P) + sum_{j<3} [z_j <= P - 1] b_j        (P >= 1)
+// with z_j = clz(S_j) (32 for 0) of S_2 = u_2 | u_3, S_1 = u_1 | S_2, S_0 = u_0 | S_1 and b_j = bit 31 - z_j of u_j.
+// Its first difference over t, F[t] = L(a - t) - L(a - t - 1), is L(1) - 1 at t = a - 1 and
+//   F[a - 1 - P] = 1 + #{j : z_j <= P} + sum_j [z_j = P] b_j                               (P = 1 .. pmax - 1):
+// a step function of P (1 + #{z_j <= P}) plus impulses (b_j at P = z_j). So a block is at most 9 updates of two 288-bin
+// arrays -- steps: + (1 + #{z_j <= 1}) at a - 2, + 1 at a - 1 - z_j for 2 <= z_j <= pmax - 1, minus their sum at
+// a - 1 - pmax; impulses: L(1) - 1 at a - 1, b_j at a - 1 - z_j for 1 <= z_j <= pmax - 1 -- and
+//   table[t] = nblocks + sum_{s >= t} (impulse[s] + sum_{r >= s} step[r]).
+// A zero block (or pmax = 0) is one bit at every t and adds nothing. Indices run from -1 (the step end of an
+// emax = -126 block at pmax = 32, dropped: the table starts at 0) to 285.
+//
+//   k_rate_table1d        RT_TILE blocks per workgroup and iteration, a grid-stride loop with the next tile's loads
+//                         issued before a tile is processed. The two arrays live in LDS as 32-bit integers, RT_COPIES
+//                         interleaved copies each (lane & 15 picks the copy): a gradient bucket puts most blocks of a
+//                         wave on the same few bins, and same-address LDS atomics serialise, so the copies cut a
+//                         64-deep conflict to 4. At the end the workgroup sums the copies and adds its non-zero bins
+//                         to the global workspace with 64-bit atomics (steps sign-extended).
+//   k_rate_table_finish   288 x 2 workspace words -> the table: both suffix sums in one backward sweep.
+// The workspace is zeroed by a memset node ahead of the first kernel; the table is written whole. Integer adds only:
+// the result does not depend on the order of the atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "codec_device.h"
+#include "field_io.h"
+#include "kernels.h"
+#include "lean1d.h"
+#include "var1d_prep.h"
+
+namespace gcow {
+
+namespace {
+
+constexpr uint32_t RTT = 256;                    // lanes per workgroup
+constexpr uint32_t RTU = 4;                      // consecutive blocks per lane
+constexpr uint32_t RT_TILE = RTT * RTU;          // blocks per workgroup and iteration
+constexpr uint32_t RT_BINS = kRateTableEntries;  // 288
+constexpr uint32_t RT_COPIES = 16;               // interleaved LDS copies of each array
+constexpr uint32_t RT_MAXGRID = 1024;            // 4 workgroups of 36 KB LDS per CU on 256 CUs
+static_assert(RT_TILE * 4 == kRateTableTileValues, "kernels.h states the tile for the tests");
+// A 32-bit LDS bin cannot wrap: a block adds at most 12 to one bin (L(1) - 1 <= 12; a step start or end is at most 4
+// in magnitude), a call has fewer than 2^32 blocks in at most 2^22 tiles, so a workgroup of a full grid sees at most
+// 2^22 / RT_MAXGRID + 1 tiles = 2^22 + 2^10 blocks, and (2^22 + 2^10) * 12 < 2^26.
+static_assert(((1ull << 32) / RT_TILE / RT_MAXGRID + 1) * RT_TILE * 12 < (1ull << 31), "LDS bins are 32-bit");
+
+// the lane's RTU consecutive blocks of a tile as raw words (fp32: one 16-byte load per block; bf16: one per two)
+template <int DT>
+struct RtRaw {
+  static constexpr int N = DT == DT_BF16 ? RTU / 2 : RTU;
+  uint4 w[N];
+  // a tile of whole blocks in a contiguous, 16-byte aligned field
+  __device__ __forceinline__ void load_wide(const FieldDesc& F, uint32_t t)
+  {
+    const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
+    const uint4* src = (const uint4*)F.data + (DT == DT_BF16 ? bl / 2 : bl);
+#pragma unroll
+    for (int h = 0; h < N; h++) w[h] = src[h];
+  }
+  // any tile: blocks past the field read nothing, the partial last block is padded as the encoder pads it
+  __device__ __forceinline__ void gather(const FieldDesc& F, uint32_t t)
+  {
+    const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
+    uint32_t* d = (uint32_t*)w;
+#pragma unroll
+    for (uint32_t k = 0; k < RTU; k++) {
+      float f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (bl + k < F.nblocks) gather_block<1, DT>(F, (uint32_t)(bl + k), f);
+      if constexpr (DT == DT_BF16) {
+        d[2 * k] = (__float_as_uint(f[0]) >> 16) | (__float_as_uint(f[1]) & 0xffff0000u);
+        d[2 * k + 1] = (__float_as_uint(f[2]) >> 16) | (__float_as_uint(f[3]) & 0xffff0000u);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[4 * k + i] = __float_as_uint(f[i]);
+      }
+    }
+  }
+  __device__ __forceinline__ void block(uint32_t k, float* f) const
+  {
+    const uint32_t* d = (const uint32_t*)w;
+    if constexpr (DT == DT_BF16) {
+      f[0] = __uint_as_float(d[2 * k] << 16);
+      f[1] = __uint_as_float(d[2 * k] & 0xffff0000u);
+      f[2] = __uint_as_float(d[2 * k + 1] << 16);
+      f[3] = __uint_as_float(d[2 * k + 1] & 0xffff0000u);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++) f[i] = __uint_as_float(d[4 * k + i]);
+    }
+  }
+};
+
+// bin t of the lane's copy; t outside the table (only -1 occurs) is dropped
+__device__ __forceinline__ void rt_add(uint32_t* h, uint32_t copy, int t, uint32_t v)
+{
+  if ((uint32_t)t < RT_BINS) atomicAdd(h + (uint32_t)t * RT_COPIES + copy, v);
+}
+
+// one block's updates; a1 = a - 1 = emax + 157, the entry at which the block has precision 1
+__device__ __forceinline__ void rt_block(uint32_t* step, uint32_t* imp, uint32_t copy, int a1, const uint32_t* u,
+                                         uint32_t pmax)
+{
+  const uint32_t S2 = u[2] | u[3], S1 = u[1] | S2, S0 = u[0] | S1;
+  const uint32_t z[3] = {min(ffbh_hw(S0), 32u), min(ffbh_hw(S1), 32u), min(ffbh_hw(S2), 32u)};
+  uint32_t l1 = 12u, start = 1u, level = 0u;  // l1 = L(1) - 1
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const uint32_t b = shl_hw(u[j], z[j]) >> 31;  // bit 31 - z_j of u_j; z_j = 32: u_j = 0
+    l1 += z[j] == 0 ? b : 0u;
+    l1 -= min(z[j], 1u);
+    start += z[j] <= 1u ? 1u : 0u;
+    const bool in = z[j] >= 1u && z[j] < pmax;
+    if (in && b) rt_add(imp, copy, a1 - (int)z[j], 1u);
+    if (in && z[j] >= 2u) {
+      rt_add(step, copy, a1 - (int)z[j], 1u);
+      level++;
+    }
+  }
+  rt_add(imp, copy, a1, l1);
+  rt_add(step, copy, a1 - 1, start);
+  rt_add(step, copy, a1 - (int)pmax, 0u - (start + level));
+}
+
+template <int DT>
+__device__ __forceinline__ void rt_tile(const FieldDesc& F, const RtRaw<DT>& raw, uint32_t t, uint32_t pmax,
+                                        uint32_t* step, uint32_t* imp, uint32_t copy)
+{
+  const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
+#pragma unroll
+  for (uint32_t k = 0; k < RTU; k++) {
+    float f[4];
+    raw.block(k, f);
+    uint32_t u[4];
+    bool inf;
+    const uint32_t m = v1_coeffs(f, u, inf);
+    int a1 = (int)(m >> 23) + 31;  // emax = E - 126
+    bool live = m != 0u;
+    if (inf) {  // Inf / NaN: the generic rule for the exponent and the cast (emax from the finite values, Inf: 0)
+      const Params full{1u, 16658u, 64u, -1074};  // precision > 0 for every emax: be = emax + 127, 0 for a zero block
+      const BlockHead h = prepare_block<1>(f, full, u);
+      a1 = (int)h.be + 30;
+      live = h.be != 0u;
+    }
+    if (live && bl + k < F.nblocks) rt_block(step, imp, copy, a1, u, pmax);
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(RTT) void k_rate_table1d(FieldDesc F, uint32_t pmax, uint32_t ntiles,
+                                                      unsigned long long* __restrict__ ws)
+{
+  __shared__ uint32_t hist[2 * RT_BINS * RT_COPIES];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < 2 * RT_BINS * RT_COPIES; i += RTT) hist[i] = 0u;
+  __syncthreads();
+  uint32_t* step = hist;
+  uint32_t* imp = hist + RT_BINS * RT_COPIES;
+  const uint32_t copy = tid & (RT_COPIES - 1u);
+  const bool wide_ok = F.vec && (((uintptr_t)F.data) & 15u) == 0;
+  const uint32_t nfull = wide_ok ? (uint32_t)(F.n[0] / 4 / RT_TILE) : 0u;  // tiles of whole blocks, loaded wide
+  RtRaw<DT> cur{}, nxt{};
+  uint32_t t = blockIdx.x;
+  if (t < nfull) cur.load_wide(F, t);
+  for (; t < ntiles; t += gridDim.x) {
+    if (t >= nfull) cur.gather(F, t);
+    const uint32_t tn = t + gridDim.x;  // < 2^22 + 2^10
+    if (tn < nfull) nxt.load_wide(F, tn);
+    rt_tile<DT>(F, cur, t, pmax, step, imp, copy);
+    cur = nxt;
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < 2 * RT_BINS; i += RTT) {
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < RT_COPIES; c++) s += hist[i * RT_COPIES + c];
+    if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
+  }
+}
+
+__global__ __launch_bounds__(RT_BINS) void k_rate_table_finish(const unsigned long long* __restrict__ ws,
+                                                               uint64_t nblocks, uint64_t* __restrict__ table)
+{
+  __shared__ uint64_t s[2 * RT_BINS];
+  const uint32_t tid = threadIdx.x;
+  s[tid] = ws[tid];
+  s[RT_BINS + tid] = ws[RT_BINS + tid];
+  __syncthreads();
+  if (tid == 0) {
+    uint64_t level = 0, acc = nblocks;
+    for (int t = (int)RT_BINS - 1; t >= 0; t--) {
+      level += s[t];
+      acc += level + s[RT_BINS + t];
+      s[t] = acc;
+    }
+  }
+  __syncthreads();
+  table[tid] = s[tid];
+}
+
+}  // namespace
+
+size_t rate_table_workspace_bytes() { return 2 * RT_BINS * sizeof(uint64_t); }
+
+hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, rate_table_workspace_bytes(), st);
+  if (e != hipSuccess) return e;
+  const uint32_t pmax = std::min(maxprec, 32u);
+  if (F.nblocks && pmax) {
+    const uint32_t ntiles = (uint32_t)(((uint64_t)F.nblocks + RT_TILE - 1) / RT_TILE);
+    const uint32_t grid = std::min(ntiles, RT_MAXGRID);
+    if (F.dtype == DT_BF16) k_rate_table1d<DT_BF16><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
+    else k_rate_table1d<DT_F32><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  k_rate_table_finish<<<1, RT_BINS, 0, st>>>((const unsigned long long*)ws, F.nblocks, table);
+  return hipGetLastError();
+}
+
+}  // namespace gcow

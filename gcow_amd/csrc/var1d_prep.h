@@ -71,6 +71,35 @@ __device__ __forceinline__ uint32_t v1_prep(const float* f, int cexp, int maxpre
   return one ? 1u : 9u + len;
 }
 
+// The front of v1_prep alone, for callers that need the coefficients but no parameter set (rate_table1d.hip): u as
+// v1_prep forms them, which do not depend on minexp (the cast scales by the block's own exponent). Returns max |f| as
+// bits: the biased exponent is E = m >> 23 (emax = E - 126), m == 0 an all-zero block. inf: Inf / NaN present (the
+// caller takes prepare_block<1>).
+__device__ __forceinline__ uint32_t v1_coeffs(const float* f, uint32_t* u, bool& inf)
+{
+  uint32_t m;
+  asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(m) : "v"(f[0]), "v"(f[1]), "v"(f[2]));
+  asm("v_max_f32_e64 %0, %0, |%1|" : "+v"(m) : "v"(f[3]));
+  inf = m > 0x7f7fffffu || __builtin_isunordered(f[0], f[1]) || __builtin_isunordered(f[2], f[3]);
+  const uint32_t E = m >> 23;
+  const float s = __uint_as_float(0x8d800000u - (m & 0x7f800000u));  // 2^(30 - emax)
+  const uint32_t tm = (uint32_t)((int32_t)(E - 29u) >> 31);          // E < 29: every value casts to INT_MIN
+  auto cast = [&](float v) { return ((uint32_t)cvt_i32_hw(v * s) & ~tm) | (tm & 0x80000000u); };
+  uint32_t x = cast(f[0]), y = cast(f[1]), z = cast(f[2]), w = cast(f[3]);
+  auto asr = [](uint32_t v) { return (uint32_t)((int32_t)v >> 1); };
+  constexpr uint32_t NB = 0xaaaaaaaau;
+  x = asr(x + w); w -= x;  // fwd_lift
+  z = asr(z + y); y -= z;
+  x = asr(x + z); z -= x;
+  w = asr(w + y); y -= w;
+  w += asr(y); y -= asr(w);
+  u[0] = (x + NB) ^ NB;
+  u[1] = (y + NB) ^ NB;
+  u[2] = (z + NB) ^ NB;
+  u[3] = (w + NB) ^ NB;
+  return m;
+}
+
 // The decode of a block no budget truncated, from v1_prep's u, hdr and K (K = 31 - kmin): an untruncated code holds
 // planes 31 .. kmin of every coefficient whole, so the decoder's coefficients are u_j with the planes below kmin
 // cleared; a block whose header is the single '0' bit (hdr = 0: a zero block, or no precision) decodes to +0. Then the

@@ -21,6 +21,10 @@ Error feedback (`GcowHookState.error_feedback`, both wire hooks): what the codec
 kept on that rank and added to its next step's bucket before encoding, so the sent gradients average over steps to
 the meant ones (codec.encode_residual: one fused kernel at rate 8 / 16, and the variable-rate encoder writing the
 residual from its own coefficients for accuracy / precision sets, which have no bit budget).
+
+Accuracy mode under a bit budget (`GcowHookState.target_bits`, all three hooks): the tolerance is fitted to a budget
+in bits per value from the bucket's rate table (codec.rate_table: the stream length under every minexp from one pass);
+roundtrip_hook bounds the budget, the wire hooks track it with a control lagged by one step.
 """
 import contextlib
 import queue
@@ -82,7 +86,28 @@ class GcowHookState:
     (bucket.gradients(), views of the buffer) is round-tripped in place as a field of its own, in accuracy mode under
     a tolerance of 2^-relative_bits relative to that gradient's largest magnitude (codec.roundtrip_tensors_relative,
     through the codec's roundtrip_relative, cached per bucket). `params` contributes only its maxprec. The bucket must
-    be fp32 or bf16. Unset (the default): nothing changes."""
+    be fp32 or bf16. Unset (the default): nothing changes.
+
+    `target_bits` (all three hooks): accuracy mode under a bit budget of target_bits bits per value. `params` must be
+    a variable-rate set without a block budget (accuracy, precision, expert with minbits <= 1 and maxbits >= 160),
+    else ValueError; it supplies maxprec and the first step's minexp. Combined with `relative_bits`: ValueError. The
+    tolerance comes from the bucket's rate table (codec.rate_table: the stream length under every minexp from one
+    pass) and codec.fit_minexp: the finest minexp whose stream fits.
+    roundtrip_hook fits the reduced bucket itself, in the `then` callback (the 2.3 KB host read happens there, off the
+    autograd thread), and round-trips it under the fitted set: the bucket is the same on every rank, so is the fit,
+    and the simulated stream is never longer than floor(target_bits * n) bits.
+    The wire hooks must encode on the autograd thread before the exchange, so their control lags one step: beside the
+    encode the hook launches the rate table of the bucket; inside the exchange the table is all-reduced (sum) over the
+    exchange group and fitted against world * floor(target_bits * n) bits, and the resulting minexp is kept on the
+    state per bucket (keyed like the error buffers, by bucket index and numel) for that bucket's encode and decode in
+    the NEXT step. Every rank holds the same summed table and applies the same rule, so every rank uses the same set
+    in every step; DDP waits for all bucket futures before the next backward, so the value is in place when the next
+    step's hook reads it. The wire hooks therefore TRACK the budget, they do not bound it: a step's streams are fitted
+    to the step before, the budget is met by the ranks' total and not by each rank, and with `error_feedback` the
+    table is taken of the bucket, not of bucket + carried error. (codec.encode_fitted and roundtrip_hook do bound
+    it.) A budget below one bit per block selects the coarsest entry. `mean_params` of `compress_mean` is not fitted.
+    `reset_error_feedback()` keeps the fitted values; `reset_rate_fit()` forgets them (the next step uses `params`).
+    Unset (the default): nothing changes and rate_table is never called."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -97,6 +122,9 @@ class GcowHookState:
     mean_params: GcowParams | None = None  # the mean's parameter set; None: `params`
     # roundtrip_hook: a tolerance relative to each parameter's gradient (class docstring); the wire hooks refuse it
     relative_bits: int | None = None
+    # accuracy mode under a budget of this many bits per value (class docstring)
+    target_bits: float | None = None
+    _fits: dict = field(default_factory=dict, repr=False)  # bucket index -> (numel, fitted minexp)
     _worker: object = field(default=None, repr=False)
     _side: dict = field(default_factory=dict, repr=False)
     _comm_group: object = field(default=None, repr=False)
@@ -175,6 +203,28 @@ class GcowHookState:
         codec parameters, or skipping a step whose gradients were discarded."""
         self._errors.clear()
 
+    def check_target(self):
+        """ValueError for a `target_bits` the hooks cannot serve (class docstring); nothing when it is unset."""
+        if self.target_bits is None:
+            return
+        if not _codec.is_nobudget(self.params) or _codec.is_fixed(self.params):
+            raise ValueError("target_bits fits accuracy mode: params must be a variable-rate set without a block "
+                             "budget (minbits <= 1, maxbits >= 160), got %r" % (self.params,))
+        if self.relative_bits is not None:
+            raise ValueError("target_bits and relative_bits both choose the tolerance: set one")
+
+    def step_params(self, index, numel: int) -> GcowParams:
+        """The set bucket `index` of `numel` values is coded under in this step: `params`, or with target_bits the
+        accuracy-mode set of the minexp fitted in the step before (a bucket whose size changed starts from `params`)."""
+        ent = self._fits.get(index) if self.target_bits is not None else None
+        if ent is None or ent[0] != numel:
+            return self.params
+        return _codec.fitted_params(self.params.maxprec, ent[1])
+
+    def reset_rate_fit(self):
+        """Forget every fitted minexp (target_bits): the next step codes under `params` again."""
+        self._fits.clear()
+
     def side_stream(self, dev):
         if dev not in self._side:
             self._side[dev] = torch.cuda.Stream(dev)
@@ -209,13 +259,42 @@ def _mean_into(cdc, flat: torch.Tensor, *args):
         flat.copy_(cdc.decode_mean(*args).to(flat.dtype))
 
 
-def _encode(state: GcowHookState, cdc, bucket, x: torch.Tensor, stride: int, slot):
-    """The wire hooks' encode of the flattened bucket x: with state.error_feedback, of x plus the bucket's carried error,
-    which is updated in place (the buffer lives on the state, so the exchange never reads it)."""
+def _encode(state: GcowHookState, cdc, bucket, x: torch.Tensor, stride: int, slot, p: GcowParams | None = None):
+    """The wire hooks' encode of the flattened bucket x under p (default: state.params): with state.error_feedback, of
+    x plus the bucket's carried error, which is updated in place (the buffer lives on the state, so the exchange never
+    reads it)."""
+    if p is None:
+        p = state.params
     if not state.error_feedback:
-        return cdc.encode(x, state.params, stride, slot=slot)
+        return cdc.encode(x, p, stride, slot=slot)
     index = bucket.index() if hasattr(bucket, "index") else None
-    return cdc.encode_residual(x, state.error_buffer(index, x), state.params, stride, slot=slot)
+    return cdc.encode_residual(x, state.error_buffer(index, x), p, stride, slot=slot)
+
+
+def _rate_table(state: GcowHookState, cdc, x: torch.Tensor, index):
+    """target_bits: launch the rate table of the flattened bucket x (beside the wire hooks' encode, or on the reduced
+    bucket in roundtrip_hook); None when the state has no target."""
+    if state.target_bits is None:
+        return None
+    if not hasattr(cdc, "rate_table"):
+        raise ValueError("target_bits needs a codec with rate_table (gcow_amd.dist.DeviceCodec)")
+    return cdc.rate_table(x, state.params.maxprec, slot=("rate", index))
+
+
+def _budget(state: GcowHookState, n: int) -> int:
+    return int(state.target_bits * n)  # floor: both are >= 0
+
+
+def _fit_next(state: GcowHookState, table: torch.Tensor, index, n: int, world: int, group):
+    """The wire hooks' shared control step, inside the exchange: the ranks' tables summed over the exchange group (the
+    length of all W streams under each minexp), fitted against W budgets, and the minexp kept for the bucket's next
+    step. The one host read (2.3 KB) blocks the comm thread only. A budget below one bit per block cannot be met:
+    the coarsest entry is taken."""
+    if world > 1:
+        dist.all_reduce(table, group=group)
+    h = table.cpu().tolist()
+    me, _ = _codec.fit_minexp(h, max(world * _budget(state, n), h[-1]))
+    state._fits[index] = (n, me)
 
 
 _RELATIVE_WIRE = ("relative_bits is for roundtrip_hook: a stream coded under per-tensor exponents needs them on the "
@@ -231,6 +310,7 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
     if state.compress_mean:
         raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
                          "roundtrip_hook puts no mean shard on the wire")
+    state.check_target()
     group = state.process_group
     buf = bucket.buffer()
     cdc = state.get_codec()
@@ -250,17 +330,23 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
                                    slot=("rel", bucket.index()))
             return t
         flat, x = _flat(t)
+        p = state.params
+        bidx = bucket.index() if hasattr(bucket, "index") else None
+        if state.target_bits is not None:  # the reduced bucket's own table: the same fit on every rank
+            table = _rate_table(state, cdc, x, bidx)
+            me, _ = _codec.fit_minexp(table, _budget(state, x.numel()))  # host read, in this callback
+            p = _codec.fitted_params(p.maxprec, me)
+            state._fits[bidx] = (x.numel(), me)
         if hasattr(cdc, "roundtrip") and flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous():
-            cdc.roundtrip(x, state.params, out=flat)  # one kernel, in place, no stream (same bits as the path below)
+            cdc.roundtrip(x, p, out=flat)  # one kernel, in place, no stream (same bits as the path below)
             return t
-        stride = 0 if _codec.is_fixed(state.params) else INDEX_STRIDE
+        stride = 0 if _codec.is_fixed(p) else INDEX_STRIDE
         # per-bucket buffers: DDP may run several buckets' callbacks before the first one's decode has read its words
-        words, _, index = cdc.encode(x, state.params, stride,
-                                     slot=("roundtrip", bucket.index() if hasattr(bucket, "index") else None))
+        words, _, index = cdc.encode(x, p, stride, slot=("roundtrip", bidx))
         if flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous():
-            cdc.decode(words, x.numel(), state.params, index=index, index_stride=stride, out=flat)  # in place
+            cdc.decode(words, x.numel(), p, index=index, index_stride=stride, out=flat)  # in place
         else:
-            out = cdc.decode(words, x.numel(), state.params, index=index, index_stride=stride)
+            out = cdc.decode(words, x.numel(), p, index=index, index_stride=stride)
             flat.copy_(out.to(flat.dtype))
         return t
 
@@ -325,14 +411,15 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
                          "compressed_allgather_hook decodes every rank's stream on every rank and sends no mean")
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
+    state.check_target()
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
     flat, x = _flat(buf)
     n = x.numel()
-    p = state.params
     cdc = state.get_codec()
     slot = bucket.index() if hasattr(bucket, "index") else None
+    p = state.step_params(slot, n)  # state.params, or with target_bits the set fitted in the step before
     if _codec.is_fixed(p):
         words, _, _ = _encode(state, cdc, bucket, x, 0, slot)
         nw = ((n + 3) // 4 * p.maxbits + 63) // 64
@@ -350,8 +437,9 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
 
         return fut.then(finish)
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot)
+    words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot, p)
     index = cdc.pack_index16(index8, n, p)  # what travels: one entry per 16 blocks
+    table = _rate_table(state, cdc, x, slot)  # target_bits: this step's lengths, for the next step's set
     dev = x.device
     if dev.type == "cuda":
         ev = torch.cuda.Event()
@@ -369,8 +457,11 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
         with ctx:
             if side is not None:
                 side.wait_event(ev)
-                for t in (words, bits, index):  # read on the side stream: keep them out of the allocator until then
-                    t.record_stream(side)
+                for t in (words, bits, index, table):  # read on the side stream: kept from the allocator until then
+                    if t is not None:
+                        t.record_stream(side)
+            if table is not None:
+                _fit_next(state, table, slot, n, world, cgroup)
             lens, lens_h = gdist.gather_lengths(bits, dev, cgroup)  # host read: this thread waits, autograd does not
             maxw = max(1, max((b + 63) // 64 for b in lens_h))
             rank = dist.get_rank(cgroup)
@@ -386,15 +477,16 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     return state.worker().submit(exchange, fut)
 
 
-def _mean_stream(state: GcowHookState, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev):
-    """compress_mean: the stream (words, bits, index) of the mean of this rank's `world` received pieces under
-    state.mean_params, with error feedback on the mean shard when the state asks for it; (None, None, None) for an
-    empty shard. Runs inside the exchange, on the side stream: the carried error and the cached encoder's buffers are
-    allocated there."""
+def _mean_stream(state: GcowHookState, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev, p=None):
+    """compress_mean: the stream (words, bits, index) of the mean of this rank's `world` received pieces (coded under
+    p; default state.params) under state.mean_params, with error feedback on the mean shard when the state asks for
+    it; (None, None, None) for an empty shard. Runs inside the exchange, on the side stream: the carried error and the
+    cached encoder's buffers are allocated there."""
     if hi <= lo:
         return None, None, None
-    p = state.params
-    mp = state.mean_params or p
+    if p is None:
+        p = state.params
+    mp = state.mean_params or state.params
     ostride = 0 if _codec.is_fixed(mp) else gdist.MEAN_INDEX_STRIDE
     err = None
     if state.error_feedback:
@@ -425,19 +517,21 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     decode_mean and encode), and the bucket ends as decode(encode(mean)) under state.mean_params on every rank."""
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
+    state.check_target()
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
     flat, x = _flat(buf)
     n = x.numel()
-    p = state.params
     cdc = state.get_codec()
+    bidx = bucket.index() if hasattr(bucket, "index") else None
+    p = state.step_params(bidx, n)  # state.params, or with target_bits the set fitted in the step before
     fixed = _codec.is_fixed(p)
     stride = 0 if fixed else SHARDED_INDEX_STRIDE
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    bidx = bucket.index() if hasattr(bucket, "index") else None
     slot = ("sharded", bidx)
-    words, bits, index = _encode(state, cdc, bucket, x, stride, slot)
+    words, bits, index = _encode(state, cdc, bucket, x, stride, slot, p)
+    table = _rate_table(state, cdc, x, bidx)  # target_bits: this step's lengths, for the next step's set
     dev = x.device
     if dev.type == "cuda":
         ev = torch.cuda.Event()
@@ -455,9 +549,11 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
         with ctx:
             if side is not None:
                 side.wait_event(ev)
-                for t in (words, bits, index):
+                for t in (words, bits, index, table):
                     if t is not None:
                         t.record_stream(side)
+            if table is not None:
+                _fit_next(state, table, bidx, n, world, cgroup)
             if fixed:
                 pieces, pw, lo, hi = gdist.shard_pieces_fixed(words, n, p.maxbits, cgroup)
                 pidx, iw = None, 0
@@ -466,8 +562,10 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
             direct = flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous()
             shard = flat[lo:hi] if direct else torch.empty(hi - lo, dtype=torch.float32, device=dev)
             if state.compress_mean:
-                mwords, mbits, midx = _mean_stream(state, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev)
-                gdist.allgather_mean_streams(flat, mwords, mbits, midx, n, state.mean_params or p, cgroup, cdc)
+                mwords, mbits, midx = _mean_stream(state, cdc, bidx, pieces, pw, world, lo, hi, pidx, iw, stride, dev,
+                                                   p)
+                gdist.allgather_mean_streams(flat, mwords, mbits, midx, n, state.mean_params or state.params, cgroup,
+                                             cdc)
                 fut.set_result(buf)
                 return
             if hi > lo:

@@ -135,6 +135,23 @@ class DeviceCodec:
         self._evict_idle()
         return ent[0](tensors)
 
+    def rate_table(self, x: torch.Tensor, maxprec: int = 64, slot=None) -> torch.Tensor:
+        """The rate table of the flattened bucket x (codec.RateTable): int64[288] on x's device, entry t the bits
+        `encode` reports under expert(1, 16658, maxprec, -154 + t). The table and workspace are cached per (slot,
+        numel, dtype, device) under the encoders' idleness rule; calls with the same key overwrite one table."""
+        from . import codec
+        x = x.reshape(-1)
+        self._tick += 1
+        key = (slot, x.numel(), x.dtype, x.device, "rate_table")
+        ent = self._enc.get(key)
+        if ent is None:
+            ent = self._enc[key] = [codec.RateTable(x.numel(), x.dtype, x.device), self._tick]
+        else:
+            ent[1] = self._tick
+            self._enc.move_to_end(key)
+        self._evict_idle()
+        return ent[0](x if x.is_contiguous() else x.contiguous(), maxprec)
+
     def pack_index16(self, index8, n: int, params):
         from . import codec
         return codec.pack_index16(index8, n, params)

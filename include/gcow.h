@@ -448,6 +448,34 @@ gcow_status gcow_roundtrip_rel_device(const void* h_plan, const void* d_plan, si
                                       uint32_t maxprec, float* d_absmax, uint64_t* d_total_bits, void* hip_stream);
 
 /*
+ * Rate table: accuracy mode under a bit budget. For a contiguous 1-D field (DEVICE, dtype_float or dtype_bf16, any
+ * element-aligned address) one pass over the input writes d_table[t], t = 0 .. GCOW_RATE_TABLE_ENTRIES - 1 (DEVICE
+ * uint64), for minexp = GCOW_RATE_TABLE_MINEXP_LO + t:
+ *   d_table[t] = the unflushed bit count of the stream gcow_encode_device writes for the field under
+ *                {minbits 1, maxbits 16658, maxprec, minexp} -- exactly the value that call stores in *d_total_bits.
+ * The range is complete: below minexp -154 every block already has its full precision, so every smaller minexp gives
+ * d_table[0]; from 132 on every block is a single bit, so d_table[286] = d_table[287] = the number of blocks and every
+ * larger minexp gives the same. The table is non-increasing in t (a plane more of precision never shortens a block).
+ * It is exact, not an estimate: integer sums only, the same bits run to run.
+ *
+ * d_workspace: gcow_rate_table_workspace_bytes(field) bytes, 8-byte aligned. Neither the table nor the workspace needs
+ * zeroing by the caller; the table is written whole and nothing past it. No host synchronisation, no allocation; legal
+ * inside a stream capture. nx = 0 gives an all-zero table.
+ * GCOW_ERR_INVALID: a field that is not 1-D or has a non-unit stride, a NULL or misaligned pointer, a workspace below
+ * the query. GCOW_ERR_UNSUPPORTED: a dtype other than float / bf16; 2^32 blocks or more.
+ *
+ * gcow_rate_table_fit (HOST; h_table: a host copy of the 288 entries): the smallest minexp in [-154, 133] whose entry
+ * is <= budget_bits -- the finest tolerance whose stream fits -- and that entry. GCOW_ERR_INVALID when budget_bits <
+ * h_table[287]: no accuracy-mode stream is shorter than one bit per block (*minexp and *bits are left alone).
+ */
+#define GCOW_RATE_TABLE_MINEXP_LO (-154)
+#define GCOW_RATE_TABLE_ENTRIES 288
+size_t gcow_rate_table_workspace_bytes(const zfp_input* field);
+gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uint64_t* d_table, void* d_workspace,
+                                   size_t workspace_bytes, void* hip_stream);
+gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, int* minexp, uint64_t* bits);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by

@@ -9,6 +9,8 @@
               chunks (codec.HostEncoder)
   var_f32     256 Mi fp32 1-D accuracy 1e-6 / 1e-3 encode
   var_decode  256 Mi fp32 1-D accuracy 1e-6 / 1e-3 decode (block index every 16 blocks)
+  rate_table  256 Mi fp32 / bf16 1-D: the rate-table pass against the accuracy-1e-3 encode, and the fitted encode end
+              to end (interleaved rounds in one process)
 Timing: HIP events on the launching stream, median of interleaved rounds.
 """
 import argparse
@@ -188,6 +190,82 @@ def c5():
              host_path_ms=round(ms_h, 3), host_path_GiBps_input=round(n * 2 / (ms_h / 1e3) / 2 ** 30, 2),
              host_overlapped_ms=round(ms_p, 3), host_overlapped_GiBps_input=round(n * 2 / (ms_p / 1e3) / 2 ** 30, 2),
              host_overlapped_chunks=len(henc.bounds))
+
+
+def timeit_interleaved(fns, reps=5, rounds=7, settle_s=0.3, host=()):
+    """Median per-call time of several callables measured in the same process, one after the other within every
+    round, so that clock and neighbour drift hit all of them alike. Device events on the launching stream; names in
+    `host` are timed with the host clock around calls that end in a device synchronise (they read back mid-call)."""
+    st = torch.cuda.current_stream()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < settle_s:
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            if k in host:
+                torch.cuda.synchronize()
+                h0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - h0) * 1e3 / reps)
+            else:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(reps):
+                    fn()
+                e1.record(st)
+                torch.cuda.synchronize()
+                ts[k].append(e0.elapsed_time(e1) / reps)
+    return {k: sorted(v)[len(v) // 2] for k, v in ts.items()}, {k: (min(v), max(v)) for k, v in ts.items()}
+
+
+def rate_table(bits_per_value=8.0):
+    """Accuracy mode under a bit budget, 256 Mi values: the rate-table pass (gcow_rate_table_device) on fp32 and
+    bf16, the full accuracy-1e-3 encode of the same bucket, the encode under the fitted set, and the fitted encode end
+    to end (table + the 2.3 KB host read + fit + encode; preallocated, as a training loop would hold them), all in
+    interleaved rounds. What a user has without the table is re-encoding until the length fits: one full encode and
+    a host read per try."""
+    n = 256 << 20
+    x = torch.empty(n, dtype=torch.float32, device="cuda")
+    codec.fill_normal(x)
+    xb = x.to(torch.bfloat16)
+    rt, rtb = codec.RateTable(n, torch.float32), codec.RateTable(n, torch.bfloat16)
+    enc3 = codec.Encoder((n,), torch.float32, codec.accuracy(1e-3))
+    enc3b = codec.Encoder((n,), torch.bfloat16, codec.accuracy(1e-3))
+    budget = int(bits_per_value * n)
+    me, fit_bits = codec.fit_minexp(rt(x), budget)
+    pf = codec.fitted_params(64, me)
+    encs = {me: codec.Encoder((n,), torch.float32, pf)}
+
+    def fitted():
+        m, _ = codec.fit_minexp(rt(x), budget)  # the host read
+        e = encs.get(m)
+        if e is None:
+            e = encs[m] = codec.Encoder((n,), torch.float32, codec.fitted_params(64, m))
+        return e(x)
+
+    assert fitted().bits == fit_bits <= budget
+    fns = {"table_f32": lambda: rt(x), "table_bf16": lambda: rtb(xb), "encode_acc1e-3_f32": lambda: enc3(x),
+           "encode_acc1e-3_bf16": lambda: enc3b(xb), "encode_fitted_set_f32": lambda: encs[me](x),
+           "fitted_end_to_end_f32": fitted}
+    med, span = timeit_interleaved(fns, host=("fitted_end_to_end_f32",))
+    for k in fns:
+        emit(case="rate_table_" + k, ms=round(med[k], 4), ms_min=round(span[k][0], 4), ms_max=round(span[k][1], 4),
+             GBps_input=round(n * (2 if k.endswith("bf16") else 4) / (med[k] / 1e3) / 1e9, 1))
+    emit(case="rate_table_summary", bits_per_value_target=bits_per_value, fitted_minexp=me,
+         fitted_bits_per_value=round(fit_bits / n, 4), acc1e3_bits_per_value=round(enc3(x).bits / n, 4),
+         table_over_encode_f32=round(med["table_f32"] / med["encode_acc1e-3_f32"], 3),
+         table_over_encode_bf16=round(med["table_bf16"] / med["encode_acc1e-3_bf16"], 3),
+         fitted_over_encode_acc1e3_f32=round(med["fitted_end_to_end_f32"] / med["encode_acc1e-3_f32"], 3),
+         fitted_over_its_own_encode_f32=round(med["fitted_end_to_end_f32"] / med["encode_fitted_set_f32"], 3))
+    t0 = time.perf_counter()  # the one-shot call allocates its encoder (stream buffer, workspace) every time
+    for _ in range(3):
+        codec.encode_fitted(x, bits_per_value)[0].bits
+    emit(case="rate_table_encode_fitted_oneshot", ms=round((time.perf_counter() - t0) * 1e3 / 3, 3))
 
 
 if __name__ == "__main__":
