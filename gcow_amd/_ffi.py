@@ -133,6 +133,9 @@ def load():
         "gcow_rate_table_workspace_bytes": (sz, [pi]),
         "gcow_rate_table_device": (i32, [pi, u32, vp, vp, sz, vp]),
         "gcow_rate_table_fit": (i32, [P(u64), u64, P(i32), P(u64)]),
+        "gcow_rate_table_fit_device": (i32, [vp, u64, vp, vp]),
+        "gcow_encode_fitted_device": (i32, [pi, u32, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
+        "gcow_roundtrip_fitted_device": (i32, [pi, u32, vp, vp, i32, vp, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),

@@ -554,7 +554,9 @@ def decode(enc_or_words, shape=None, params: GcowParams | None = None, index: to
     the fp32 decode rounded to nearest even, as `.to(torch.bfloat16)`)."""
     if isinstance(enc_or_words, Encoded):
         e = enc_or_words
-        words, shape, params = e.words, e.shape, e.params
+        words, shape = e.words, e.shape
+        if e.params is not None:  # None: a fitted stream (FittedEncoder), decoded under the params the caller read
+            params = e.params
         if index is None and e.index is not None:
             index, index_stride = e.index, e.index_stride
     else:
@@ -651,6 +653,147 @@ def encode_fitted(x: torch.Tensor, bits_per_value: float, maxprec: int = 64, ind
     Encoded.bits <= floor(bits_per_value * n): the table entry is the encoder's own bit count."""
     p = fit_accuracy(x, bits_per_value, maxprec, stream)
     return encode(x, p, index_stride, stream), p
+
+
+# ------------------------------------------------------------------------------------------- the fit on the device
+# A gcow_fit record (include/gcow.h) as a device tensor: int64[2], word 0 = minexp (low half, signed) | status << 32,
+# word 1 = bits. Its first 4 bytes are the int32 word the fitted calls read.
+FIT_WORDS = 2
+
+
+def new_fit_record(device=None) -> torch.Tensor:
+    return torch.zeros(FIT_WORDS, dtype=torch.int64, device=torch.device(device or "cuda"))
+
+
+def read_fit(fit: torch.Tensor):
+    """-> (minexp, status, bits) of a gcow_fit record: the host read of its 16 bytes (a synchronisation when the record
+    is on the device)."""
+    w0, w1 = (int(v) for v in fit.detach().reshape(-1)[:FIT_WORDS].cpu().tolist())
+    me = w0 & 0xFFFFFFFF
+    return (me - (1 << 32) if me >> 31 else me), (w0 >> 32) & 0xFFFFFFFF, w1 & ((1 << 64) - 1)
+
+
+def _budget_u64(budget_bits) -> int:
+    return min(max(int(budget_bits), 0), (1 << 64) - 1)
+
+
+def fit_device(table: torch.Tensor, budget_bits: int, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """gcow_rate_table_fit_device: the fit of a device rate table (int64[288], one bucket's or a sum over ranks)
+    against budget_bits, written to the gcow_fit record `out` (default: a new one) by one small kernel. Nothing is
+    read on the host; the record equals fit_minexp's answer with status 0, or the coarsest set (minexp 133) with
+    status 1 where fit_minexp raises. Returns the record: pass it to encode_fitted_device / roundtrip_fitted as the
+    minexp word, read it with read_fit."""
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int64
+            and table.numel() == RATE_TABLE_ENTRIES and table.is_contiguous()):
+        raise GcowError("fit_device: table must be a contiguous int64[%d] device tensor" % RATE_TABLE_ENTRIES)
+    if out is None:
+        out = new_fit_record(table.device)
+    if not (out.is_cuda and out.device == table.device and out.dtype == torch.int64 and out.numel() >= FIT_WORDS
+            and out.is_contiguous()):
+        raise GcowError("fit_device: out must be a contiguous int64[%d] tensor on the table's device" % FIT_WORDS)
+    check(load().gcow_rate_table_fit_device(table.data_ptr(), _budget_u64(budget_bits), out.data_ptr(),
+                                            _stream_ptr(stream)), "gcow_rate_table_fit_device")
+    return out
+
+
+def _minexp_ptr(word: torch.Tensor, device) -> int:
+    if not (isinstance(word, torch.Tensor) and word.is_cuda and word.device == device and word.numel() >= 1
+            and word.dtype in (torch.int32, torch.int64) and word.is_contiguous()):
+        raise GcowError("minexp_word must be an int32 tensor (or a gcow_fit record from fit_device) on x's device")
+    return word.data_ptr()
+
+
+class FittedEncoder:
+    """Accuracy mode under a bit budget with no host read: preallocated rate table, gcow_fit record, stream, bit count,
+    index and workspace for 1-D buckets of n values. Calling it with x launches the table pass, the device fit against
+    floor(bits_per_value * n) bits and gcow_encode_fitted_device, which takes minexp from the record, and returns an
+    Encoded whose `params` is None -- the set is on the device. The call allocates nothing and synchronises nothing,
+    so it can be captured into a graph that then follows the data it is replayed on. `fit` is the device record;
+    `params()` reads it (the only synchronisation) for codec.decode. The stream is byte for byte
+    codec.encode_fitted's whenever the budget can be met (status 0)."""
+
+    def __init__(self, n: int, dtype, bits_per_value: float, maxprec: int = 64, device=None, index_stride: int = 0):
+        self.n, self.dtype, self.maxprec = int(n), dtype, int(maxprec)
+        self.device = torch.device(device or "cuda")
+        self.budget = int(math.floor(bits_per_value * self.n))
+        self.table = RateTable(self.n, dtype, self.device)
+        self.fit = new_fit_record(self.device)
+        # capacity and workspace do not depend on minexp (include/gcow.h): sized from any set of this maxprec
+        self.enc = Encoder((self.n,), dtype, fitted_params(self.maxprec, 0), self.device, index_stride)
+        self.L = self.enc.L
+
+    def __call__(self, x: torch.Tensor, stream=None) -> Encoded:
+        self.table(x, self.maxprec, stream)  # checks x
+        fit_device(self.table.table, self.budget, self.fit, stream)
+        return _encode_fitted_into(self.enc, x, self.fit, stream)
+
+    def params(self, allow_coarsest: bool = False) -> GcowParams:
+        """fitted_params(maxprec, the fitted minexp), from one host read of the record. GcowError when the budget was
+        below one bit per block and the coarsest set was taken (status 1), unless allow_coarsest."""
+        me, status, _ = read_fit(self.fit)
+        if status and not allow_coarsest:
+            raise GcowError("budget of %d bits is below one bit per block: the coarsest set was used "
+                            "(allow_coarsest=True accepts it)" % self.budget)
+        return fitted_params(self.maxprec, me)
+
+
+def _encode_fitted_into(enc: Encoder, x: torch.Tensor, minexp_word: torch.Tensor, stream=None) -> Encoded:
+    if x.dim() != 1 or tuple(x.shape) != enc.shape or x.dtype != enc.dtype:
+        raise GcowError("fitted encoder built for %s %s, got %s %s" % (enc.shape, enc.dtype, tuple(x.shape), x.dtype))
+    if not (x.is_cuda and x.is_contiguous()):
+        raise GcowError("encode_fitted_device expects a contiguous 1-D device tensor")
+    f = field_of(x) if x.numel() else field_of_shape((0,), x.dtype)
+    st = enc.L.gcow_encode_fitted_device(C.byref(f), enc.params.maxprec, _minexp_ptr(minexp_word, x.device),
+                                         enc.words.data_ptr(), enc.cap, enc.bits_dev.data_ptr(), enc.ws.data_ptr(),
+                                         enc.ws_bytes, enc.index.data_ptr() if enc.index is not None else None,
+                                         enc.index_stride, _stream_ptr(stream))
+    check(st, "gcow_encode_fitted_device")
+    return Encoded(enc.words, enc.bits_dev, enc.shape, None, enc.index, enc.index_stride)
+
+
+def encode_fitted_device(x: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64, index_stride: int = 0,
+                         stream=None) -> Encoded:
+    """gcow_encode_fitted_device: x (contiguous 1-D device tensor, fp32 / bf16) encoded under
+    expert(1, 16658, maxprec, clamp(minexp_word[0], -154, 133)), the word (an int32 device tensor, or a gcow_fit record
+    from fit_device) read on the device when the kernels run. Byte for byte codec.encode under that set. The returned
+    Encoded has params None: decode with the params read from the record."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("dtype %s not supported (float32, bfloat16)" % x.dtype)
+    if not x.is_cuda:
+        raise GcowError("encode_fitted_device expects a device tensor")
+    enc = Encoder((x.numel(),), x.dtype, fitted_params(maxprec, 0), x.device, index_stride)
+    return _encode_fitted_into(enc, x, minexp_word, stream)
+
+
+def roundtrip_fitted(x: torch.Tensor, fit, maxprec: int = 64, out: torch.Tensor | None = None,
+                     bits: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """codec.roundtrip under a set fitted on the device (gcow_roundtrip_fitted_device). `fit` is either a number --
+    bits per value: x's rate table and its device fit against floor(fit * n) bits are launched first -- or a minexp
+    word (an int32 device tensor or a gcow_fit record). No host read either way. x, out, bits as codec.roundtrip's;
+    returns out."""
+    if not (x.is_cuda and x.is_contiguous() and x.dim() >= 1):
+        raise GcowError("roundtrip_fitted expects a contiguous device tensor")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("roundtrip_fitted: dtype %s not supported (float32, bfloat16)" % x.dtype)
+    if out is None:
+        out = torch.empty_like(x)
+    if not (out.is_cuda and out.device == x.device and out.is_contiguous() and out.numel() == x.numel()
+            and out.dtype in (torch.float32, torch.bfloat16)):
+        raise GcowError("roundtrip_fitted: out must be a contiguous fp32 or bf16 tensor of x.numel() values on x's "
+                        "device")
+    if bits is not None and not (bits.is_cuda and bits.device == x.device and bits.dtype == torch.int64
+                                 and bits.numel() == 1):
+        raise GcowError("roundtrip_fitted: bits must be a one-element int64 tensor on x's device")
+    flat = x.view(-1)
+    if not isinstance(fit, torch.Tensor):
+        budget = int(math.floor(fit * flat.numel()))
+        fit = fit_device(rate_table(flat, maxprec, stream), budget, stream=stream)
+    f = field_of(flat) if flat.numel() else field_of_shape((0,), x.dtype)
+    st = load().gcow_roundtrip_fitted_device(C.byref(f), int(maxprec), _minexp_ptr(fit, x.device), out.data_ptr(),
+                                             DTYPE_BF16 if out.dtype == torch.bfloat16 else DTYPE_FLOAT,
+                                             bits.data_ptr() if bits is not None else None, _stream_ptr(stream))
+    check(st, "gcow_roundtrip_fitted_device")
+    return out
 
 
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):

@@ -1029,6 +1029,97 @@ gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, i
   return fail(GCOW_ERR_INVALID, "budget below one bit per block: no accuracy-mode stream is that short");
 }
 
+// ---------------------------------------------------------------------------------------------- the fit on the device
+static_assert(sizeof(gcow_fit) == sizeof(gcow::RateFit) && offsetof(gcow_fit, minexp) == offsetof(gcow::RateFit, minexp) &&
+              offsetof(gcow_fit, status) == offsetof(gcow::RateFit, status) &&
+              offsetof(gcow_fit, bits) == offsetof(gcow::RateFit, bits), "gcow.h and kernels.h agree");
+
+gcow_status gcow_rate_table_fit_device(const uint64_t* d_table, uint64_t budget_bits, gcow_fit* d_fit, void* hip_stream)
+{
+  if (!d_table || (uintptr_t)d_table % 8) return fail(GCOW_ERR_INVALID, "null or misaligned table");
+  if (!d_fit || (uintptr_t)d_fit % 8) return fail(GCOW_ERR_INVALID, "null or misaligned fit record");
+  GCOW_HIP(gcow::launch_rate_table_fit(d_table, budget_bits, (gcow::RateFit*)d_fit, hip_stream));
+  return GCOW_OK;
+}
+
+// The set the fitted calls stand for on the host: everything but minexp, which no host decision reads
+// (block_bits_bound, make_plan, gcow_max_output_bytes and gcow_encode_workspace_bytes do not).
+static gcow_params fitted_host_params(uint32_t maxprec) { return gcow_params{1u, 16658u, maxprec, 0}; }
+
+static gcow_status fitted_field(const zfp_input* field, const int32_t* d_minexp, const char* what)
+{
+  if (!field) return fail(GCOW_ERR_INVALID, "null field");
+  if (field->ny || field->nz || field->nw) return fail(GCOW_ERR_UNSUPPORTED, std::string(what) + " takes 1-D fields");
+  if (field->sx != 0 && field->sx != 1)
+    return fail(GCOW_ERR_UNSUPPORTED, std::string(what) + " takes contiguous fields");
+  if (field->dtype != dtype_float && field->dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, std::string(what) + " supports dtype_float and dtype_bf16 fields");
+  if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+  return GCOW_OK;
+}
+
+gcow_status gcow_encode_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp, void* d_out,
+                                      size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                      size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                      void* hip_stream)
+{
+  gcow_status st = fitted_field(field, d_minexp, "encode_fitted");
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if ((uintptr_t)d_total_bits % 8 || (uintptr_t)d_index % 8 || (uintptr_t)d_workspace % 8 || (uintptr_t)d_out % 8)
+    return fail(GCOW_ERR_INVALID, "misaligned output, d_total_bits, d_index or workspace");
+  uint32_t shift = 0;
+  if (d_index) {
+    if (!index_stride || index_stride > 256 || (index_stride & (index_stride - 1)))
+      return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+    while ((1u << shift) < index_stride) shift++;
+  }
+  if (field->nx == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
+  if ((uintptr_t)field->data % (field->dtype == dtype_bf16 ? 2 : 4))
+    return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+  gcow::FieldDesc F;
+  if ((st = make_field(field, F, false))) return st;
+  if (out_capacity < gcow_max_output_bytes(field, &hp))
+    return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_max_output_bytes()");
+  if (!d_workspace || workspace_bytes < gcow_encode_workspace_bytes(field, &hp))
+    return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_workspace_bytes()");
+  GCOW_HIP(gcow::launch_encode1d_var_tile_fitted(F, maxprec, d_minexp, (uint32_t*)d_out, (uint64_t*)d_workspace,
+                                                 d_total_bits, d_index, shift, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp, void* d_out,
+                                         data_type out_dtype, uint64_t* d_total_bits, void* hip_stream)
+{
+  gcow_status st = fitted_field(field, d_minexp, "roundtrip_fitted");
+  if (st) return st;
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if (out_dtype != dtype_float && out_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "roundtrip writes dtype_float or dtype_bf16");
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  const size_t esz_in = field->dtype == dtype_bf16 ? 2 : 4, esz_out = out_dtype == dtype_bf16 ? 2 : 4;
+  if ((uintptr_t)field->data % esz_in || (uintptr_t)d_out % esz_out)
+    return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+  if ((uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "misaligned d_total_bits");
+  if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+  if (field->nx == 0) return GCOW_OK;
+  if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
+  gcow::FieldDesc F;
+  if ((st = make_field(field, F, false))) return st;
+  const bool rows16 = (((uintptr_t)field->data | (uintptr_t)d_out) % 16) == 0;
+  GCOW_HIP(gcow::launch_roundtrip1d_fitted(F.data, (int)F.dtype, F.n[0], maxprec, d_minexp, rows16, d_out,
+                                           out_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32, d_total_bits,
+                                           hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- round trip, tensor list
 // Rows of a direct chunk must start at a multiple of this many bytes: 4 (multi-dword buffer accesses are dword-aligned),
 // for either element type. GCOW_RTL_NATURAL_ROWS builds the fallback rule instead: the row's own size, 16 bytes (fp32)

@@ -190,6 +190,28 @@ constexpr uint32_t kRateTableEntries = 288;
 constexpr uint32_t kRateTableTileValues = 4096;
 size_t rate_table_workspace_bytes();
 hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream);
+// The fit on the device (rate_table1d.hip k_rate_table_fit; include/gcow.h gcow_fit has this layout): the smallest t
+// with table[t] <= budget -> {kRateTableMinExpLo + t, 0, table[t]}; none -> {the last entry's minexp, 1, table[287]}.
+// One workgroup of kRateTableEntries lanes; the record is written with plain stores and nothing past it.
+struct RateFit {
+  int32_t minexp;
+  uint32_t status;
+  uint64_t bits;
+};
+static_assert(sizeof(RateFit) == 16 && alignof(RateFit) == 8, "gcow_fit");
+hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, RateFit* fit, void* stream);
+// Device-parameter ("fitted") forms: Params{1, 16658, maxprec, clamp(*d_minexp, -154, 133)} with the word read on the
+// device when the kernels run (fitted_params_dev, var1d_prep.h). Nothing on the host depends on minexp.
+// The tile form of the 1-D variable-rate encoder (var1d.hip), ws = var1d_tile_workspace_bytes(): every output as
+// launch_encode1d_var_tile writes it under that set (no d_base). Always the tile form: g_var1d_variant does not apply.
+hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
+                                           uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                           uint32_t index_shift, void* stream);
+// launch_roundtrip1d under that set: rows16 (in and out 16-byte aligned) selects kRoundtripVar with the generic kernel
+// for the partial last block, else kRoundtripGeneric throughout. total as launch_roundtrip1d's.
+hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nvals, uint32_t maxprec,
+                                     const int32_t* d_minexp, bool rows16, void* out, int out_dtype, uint64_t* total,
+                                     void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

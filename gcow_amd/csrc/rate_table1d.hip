@@ -23,8 +23,11 @@
 //                         64-deep conflict to 4. At the end the workgroup sums the copies and adds its non-zero bins
 //                         to the global workspace with 64-bit atomics (steps sign-extended).
 //   k_rate_table_finish   288 x 2 workspace words -> the table: both suffix sums in one backward sweep.
-// The workspace is zeroed by a memset node ahead of the first kernel; the table is written whole. Integer adds only:
-// the result does not depend on the order of the atomics.
+//   k_rate_table_zero     the workspace zeroed in stream order ahead of the first kernel. A kernel and not a memset:
+//                         in a captured graph that also holds the fit and the encoder (FittedEncoder), the memset
+//                         node's fill wrote a stale 16-byte pattern from the second replay on (the workspace then held
+//                         that pattern plus the pass's own counts, and the table was garbage).
+// The table is written whole. Integer adds only: the result does not depend on the order of the atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -185,6 +188,12 @@ __global__ __launch_bounds__(RTT) void k_rate_table1d(FieldDesc F, uint32_t pmax
   }
 }
 
+__global__ __launch_bounds__(RT_BINS) void k_rate_table_zero(unsigned long long* __restrict__ ws)
+{
+  ws[threadIdx.x] = 0ull;
+  ws[RT_BINS + threadIdx.x] = 0ull;
+}
+
 __global__ __launch_bounds__(RT_BINS) void k_rate_table_finish(const unsigned long long* __restrict__ ws,
                                                                uint64_t nblocks, uint64_t* __restrict__ table)
 {
@@ -205,14 +214,41 @@ __global__ __launch_bounds__(RT_BINS) void k_rate_table_finish(const unsigned lo
   table[tid] = s[tid];
 }
 
+// The fit (gcow_rate_table_fit_device): the table is non-increasing, so the entries within the budget are a suffix and
+// the answer is the smallest index among them -- a min over the lanes whose entry fits, one LDS atomic each. No entry
+// fits: the coarsest set, flagged.
+__global__ __launch_bounds__(RT_BINS) void k_rate_table_fit(const uint64_t* __restrict__ table, uint64_t budget,
+                                                            RateFit* __restrict__ fit)
+{
+  __shared__ uint32_t best;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) best = RT_BINS;
+  __syncthreads();
+  const uint64_t v = table[tid];
+  if (v <= budget) atomicMin(&best, tid);
+  __syncthreads();
+  if (tid == min(best, RT_BINS - 1u)) {  // the lane that holds the chosen entry
+    fit->minexp = kRateTableMinExpLo + (int32_t)tid;
+    fit->status = best == RT_BINS ? 1u : 0u;
+    fit->bits = v;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, RateFit* fit, void* stream)
+{
+  k_rate_table_fit<<<1, RT_BINS, 0, (hipStream_t)stream>>>(table, budget_bits, fit);
+  return hipGetLastError();
+}
 
 size_t rate_table_workspace_bytes() { return 2 * RT_BINS * sizeof(uint64_t); }
 
 hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream)
 {
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, rate_table_workspace_bytes(), st);
+  k_rate_table_zero<<<1, RT_BINS, 0, st>>>((unsigned long long*)ws);
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint32_t pmax = std::min(maxprec, 32u);
   if (F.nblocks && pmax) {

@@ -171,4 +171,104 @@ hipError_t launch_roundtrip1d(const void* in, int in_dtype, uint64_t nvals, cons
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ minexp from the device
+// gcow_roundtrip_fitted_device (include/gcow.h): kernels (b) and (c) under
+// Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernel runs (fitted_params_dev, var1d_prep.h).
+// rt_var_chunk issues its U row loads from inline asm and waits vmcnt(U - 1) per block by hand. The word is loaded and
+// waited for before the first of them is issued (fitted_params_dev<true>), and as a uniform load from a kernel argument
+// it is a scalar load, which vmcnt does not count: the rule of rt_var_block (N = U - 1 for every block) holds as it
+// stands. The generic kernel has no hand-counted wait.
+template <int DT_IN, int DT_OUT, bool COUNT, int U = GCOW_RT_U>
+__global__ __launch_bounds__(256) void k_roundtrip1d_var_fitted(const void* in, uint32_t nfull, uint32_t maxprec,
+                                                                const int32_t* __restrict__ d_minexp, void* out,
+                                                                uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  const Params p = fitted_params_dev<true>(maxprec, d_minexp);
+  constexpr uint32_t IB = rt_row_bytes<DT_IN>(), OB = rt_row_bytes<DT_OUT>();
+  const pipe_v4i rin = buf_rsrc(in, nfull * IB);
+  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(nfull * OB), 0x00020000);
+  const uint32_t b0 = blockIdx.x * (256u * U) + threadIdx.x;
+  const uint32_t lsum = rt_var_chunk<DT_IN, DT_OUT, COUNT, U>(rin, rout, b0, nfull, p);
+  if constexpr (COUNT) rt_count(lsum, cnt_sh, total);
+}
+
+template <int DT_IN, int DT_OUT>
+__global__ __launch_bounds__(256) void k_roundtrip1d_generic_fitted(const void* in, uint64_t nvals, uint64_t b0,
+                                                                    uint64_t nb, uint32_t maxprec,
+                                                                    const int32_t* __restrict__ d_minexp, void* out,
+                                                                    uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  uint32_t len = 0;
+  if (i < nb) {
+    const uint64_t x0 = 4ull * (b0 + i);
+    const uint32_t nv = (uint32_t)min<uint64_t>(4, nvals - x0);
+    float f[4], d[4];
+#pragma unroll
+    for (uint32_t x = 0; x < 4u; x++) f[x] = load_elem<DT_IN>(in, (int64_t)(x0 + pad_index(x, nv)));
+    len = rt_block_generic(f, p, d);
+#pragma unroll
+    for (uint32_t x = 0; x < 4u; x++)
+      if (x < nv) {
+        if constexpr (DT_OUT == DT_BF16) ((uint16_t*)out)[x0 + x] = (uint16_t)bf16_rne(d[x]);
+        else ((float*)out)[x0 + x] = d[x];
+      }
+  }
+  if (total) rt_count(len, cnt_sh, total);  // total: a kernel argument, uniform over the workgroup
+}
+
+template <int DT_IN, int DT_OUT>
+static void launch_rt_generic_fitted(const void* in, uint64_t nvals, uint64_t b0, uint64_t nb, uint32_t maxprec,
+                                     const int32_t* d_minexp, void* out, uint64_t* total, hipStream_t st)
+{
+  constexpr uint64_t CH = 1ull << 30;  // blocks per launch: the grid stays below 2^31 workgroups
+  for (uint64_t c0 = 0; c0 < nb; c0 += CH) {
+    const uint64_t nc = std::min(CH, nb - c0);
+    k_roundtrip1d_generic_fitted<DT_IN, DT_OUT><<<(uint32_t)((nc + 255) / 256), 256, 0, st>>>(
+        in, nvals, b0 + c0, nc, maxprec, d_minexp, out, total);
+  }
+}
+
+template <int DT_IN, int DT_OUT>
+static void launch_rt_fitted_t(const void* in, uint64_t nvals, uint32_t maxprec, const int32_t* d_minexp, bool rows16,
+                               void* out, uint64_t* total, hipStream_t st)
+{
+  const uint64_t nblocks = (nvals + 3) / 4;
+  if (!rows16) {
+    launch_rt_generic_fitted<DT_IN, DT_OUT>(in, nvals, 0, nblocks, maxprec, d_minexp, out, total, st);
+    return;
+  }
+  const uint32_t nfull = (uint32_t)(nvals / 4);
+  constexpr uint32_t CH = 1u << 27;  // launch_rt_t's chunks: every buffer offset stays below 2^32
+  constexpr uint32_t IB = rt_row_bytes<DT_IN>(), OB = rt_row_bytes<DT_OUT>();
+  constexpr int U = GCOW_RT_U;
+  for (uint32_t c0 = 0; c0 < nfull; c0 += CH) {
+    const uint32_t nc = std::min(CH, nfull - c0);
+    const void* ic = (const char*)in + (size_t)c0 * IB;
+    void* oc = (char*)out + (size_t)c0 * OB;
+    const uint32_t g = (nc + 256 * U - 1) / (256 * U);
+    if (total) k_roundtrip1d_var_fitted<DT_IN, DT_OUT, true><<<g, 256, 0, st>>>(ic, nc, maxprec, d_minexp, oc, total);
+    else k_roundtrip1d_var_fitted<DT_IN, DT_OUT, false><<<g, 256, 0, st>>>(ic, nc, maxprec, d_minexp, oc, nullptr);
+  }
+  if (nvals % 4) launch_rt_generic_fitted<DT_IN, DT_OUT>(in, nvals, nfull, 1, maxprec, d_minexp, out, total, st);
+}
+
+hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nvals, uint32_t maxprec,
+                                     const int32_t* d_minexp, bool rows16, void* out, int out_dtype, uint64_t* total,
+                                     void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == DT_F32) {
+    if (out_dtype == DT_F32) launch_rt_fitted_t<DT_F32, DT_F32>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
+    else launch_rt_fitted_t<DT_F32, DT_BF16>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
+  } else {
+    if (out_dtype == DT_F32) launch_rt_fitted_t<DT_BF16, DT_F32>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
+    else launch_rt_fitted_t<DT_BF16, DT_BF16>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace gcow

@@ -1369,4 +1369,197 @@ hipError_t launch_encode_resid1d_var(const void* x, int x_dtype, uint64_t nvals,
   return launch_resid1d_var_t<DT_F32>(F, p, e_in, e_out, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------------- tile form, minexp from device memory
+// gcow_encode_fitted_device (include/gcow.h): the tile form above under
+// Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernels run -- a fit that a kernel earlier in the
+// stream wrote (k_rate_table_fit) needs no host read in between, and a captured graph follows the data it is replayed
+// on. Nothing on the host depends on minexp: the workspace layout, the scan and the oversized-tile list are the tile
+// form's own. Each kernel builds its Params once at the top (fitted_params_dev, var1d_prep.h) and runs the tile
+// form's device functions unchanged.
+//   k_count1d_var_tile_fitted      k_count1d_var_tile's body. Its ring of raw buffer loads is waited for with
+//                                  hand-counted vmcnt; the minexp word is loaded AND waited for before the ring's
+//                                  first load is issued (fitted_params_dev<true> ends in an asm that takes the
+//                                  value in an SGPR), and it is a scalar load, which vmcnt does not count: the counts of
+//                                  v1_wait_tiles hold as they stand. The cost is one scalar-cache round trip per
+//                                  workgroup of 8 tiles ahead of its loads.
+//   k_encode1d_var_tile_fitted     k_encode1d_var_tile: the word's load is issued with the tile's other loads (all
+//   k_encode1d_var_tile_big_fitted compiler-managed there, no hand-counted wait) and first used after them.
+template <int DT>
+__global__ __launch_bounds__(V1T) void k_count1d_var_tile_fitted(FieldDesc F, uint32_t maxprec,
+                                                                 const int32_t* __restrict__ d_minexp, uint32_t ntiles,
+                                                                 uint64_t* __restrict__ sums,
+                                                                 uint32_t* __restrict__ lens8,
+                                                                 uint32_t* __restrict__ nover,
+                                                                 uint64_t* __restrict__ gsums)
+{
+  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
+  const Params p = fitted_params_dev<true>(maxprec, d_minexp);  // loaded and waited for: nothing outstanding here
+  __shared__ uint32_t red[V1CT][V1T / 64];
+  const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
+  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile_fitted starts empty
+  const bool wide_ok = F.vec && (((uintptr_t)F.data) & 15u) == 0;
+  constexpr int NL = V1Raw<DT>::N;                                 // 16-byte loads per lane per tile
+  constexpr uint32_t TB = V1TILE * (DT == DT_BF16 ? 8u : 16u);     // bytes per tile
+  uint32_t packed[V1CT];
+  if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
+    const v1_v4i rs = v1_rsrc((const char*)F.data + (size_t)t0 * TB, V1CT * TB);
+    // k_count1d_var_tile's ring: tile i + PF is requested before tile i is counted
+    constexpr uint32_t PF = V1_COUNT_PF, RING = PF + 1;
+    v1_u4 buf[RING][NL];
+#pragma unroll
+    for (uint32_t i = 0; i < PF && i < V1CT; i++)
+#pragma unroll
+      for (int h = 0; h < NL; h++) buf[i][h] = v1_ld16(i * TB + (tid * NL + h) * 16u, rs);
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      if (i + PF < V1CT) {
+#pragma unroll
+        for (int h = 0; h < NL; h++) buf[(i + PF) % RING][h] = v1_ld16((i + PF) * TB + (tid * NL + h) * 16u, rs);
+      }
+      // loads issued after tile i's: those of tiles i + 1 .. min(i + PF, V1CT - 1)
+      v1_wait_tiles<NL>(buf[i % RING], (i + PF < V1CT ? PF : V1CT - 1 - i));
+      V1Raw<DT> cur;
+#pragma unroll
+      for (int h = 0; h < NL; h++) {
+        const v1_u4 v = buf[i % RING][h];
+        cur.w[h] = make_uint4(v.x, v.y, v.z, v.w);
+      }
+      uint32_t lsum;
+      packed[i] = v1_count_tile<DT, true>(F, p, cur, t0 + i, lsum);
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  } else {  // partial tiles, the padded last block, strided or unaligned input
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      uint32_t lsum = 0;
+      packed[i] = 0;
+      if (t0 + i < ntiles) {
+        V1Raw<DT> raw;
+        raw.load(F, t0 + i, wide_ok);
+        packed[i] = v1_count_tile<DT>(F, p, raw, t0 + i, lsum);
+      }
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < V1CT; i++)
+    if (t0 + i < ntiles) lens8[(size_t)(t0 + i) * V1T + tid] = packed[i];
+  __syncthreads();
+  if (tid < 64) {  // wave 0: the tile totals, and their sum for the scan's group totals
+    uint64_t tot = 0;
+    if (tid < V1CT && t0 + tid < ntiles) {
+#pragma unroll
+      for (uint32_t w = 0; w < V1T / 64; w++) tot += red[tid][w];
+      sums[t0 + tid] = tot;
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)tot, o, 64), hi = __shfl_xor((uint32_t)(tot >> 32), o, 64);
+      tot += (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    if (tid == 0) gsums[blockIdx.x] = tot;
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_fitted(FieldDesc F, uint32_t maxprec,
+                                                                  const int32_t* __restrict__ d_minexp,
+                                                                  const uint64_t* __restrict__ rbase,
+                                                                  const uint32_t* __restrict__ lens8,
+                                                                  uint32_t* __restrict__ out32,
+                                                                  uint64_t* __restrict__ index, uint32_t index_shift,
+                                                                  uint32_t ntiles, uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t t = blockIdx.x;
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  // as in k_encode1d_var_tile, every load the tile needs is issued before anything else waits
+  V1Raw<DT> raw;
+  raw.load(F, t, F.vec && (((uintptr_t)F.data) & 15u) == 0);
+  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  const uint64_t B = rbase[t];
+  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for k_encode1d_var_tile_big_fitted (over[0] = count)
+    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
+    return;
+  }
+  v1_tile_code<DT>(F, p, t, B, raw, lw, index, index_shift, tab, rs, win, scan_sh, &s_special);
+  v1_tile_store(t, B, total, win, out32, ntiles);
+}
+
+template <int DT>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_fitted(FieldDesc F, uint32_t maxprec,
+                                                                      const int32_t* __restrict__ d_minexp,
+                                                                      const uint64_t* __restrict__ rbase,
+                                                                      const uint32_t* __restrict__ lens8,
+                                                                      uint32_t* __restrict__ out32,
+                                                                      uint64_t* __restrict__ index,
+                                                                      uint32_t index_shift, uint32_t ntiles,
+                                                                      const uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t n = over[0];
+  if (blockIdx.x >= n) return;
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t t = over[1 + i];
+    const uint64_t B = rbase[t];
+    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+    v1_tile<DT>(F, p, t, B, total, lens8, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
+    __syncthreads();  // the window and scan slots are reused by the next tile
+  }
+}
+
+template <int DT>
+static hipError_t launch_fitted1d_t(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp, uint32_t* out32,
+                                    uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
+                                    hipStream_t st)
+{
+  // the tile form's workspace layout (launch_encode1d_var_tile)
+  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
+  uint64_t* sums = ws;
+  uint64_t* base = ws + ntiles;
+  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
+  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
+  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
+  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
+  k_count1d_var_tile_fitted<DT><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, ntiles, sums, lens8, over, gsums);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
+  if (e != hipSuccess) return e;
+  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
+  k_encode1d_var_tile_fitted<DT><<<ntiles, V1T, 0, st>>>(F, maxprec, d_minexp, base, lens8, out32, index, index_shift,
+                                                         ntiles, over);
+  k_encode1d_var_tile_big_fitted<DT><<<nbig, V1T, 0, st>>>(F, maxprec, d_minexp, base, lens8, out32, index,
+                                                           index_shift, ntiles, over);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
+                                           uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                           uint32_t index_shift, void* stream)
+{
+  if (F.dtype == DT_BF16)
+    return launch_fitted1d_t<DT_BF16>(F, maxprec, d_minexp, out32, ws, d_total, index, index_shift,
+                                      (hipStream_t)stream);
+  return launch_fitted1d_t<DT_F32>(F, maxprec, d_minexp, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
+}
+
 }  // namespace gcow

@@ -136,4 +136,22 @@ __device__ __forceinline__ uint32_t resid_bits(float y, float d)
   return (r & 0x7f800000u) == 0x7f800000u ? 0u : r;
 }
 
+// The parameter set of the device-parameter ("fitted") kernels (gcow_encode_fitted_device, gcow_roundtrip_fitted_device,
+// include/gcow.h): accuracy mode at the minexp a word of device memory holds, clamped to the rate table's range
+// [-154, 133] -- outside it the stream no longer changes (gcow.h "the range is complete"), and inside it emax - minexp
+// cannot leave int whatever the word holds. Called once at the top of a kernel: the address is a kernel argument, so
+// the load is uniform (a scalar load, which counts in lgkmcnt and not in vmcnt).
+// WAITED, for kernels that issue loads from inline asm and count vmcnt by hand: the empty asm takes the clamped value
+// in an SGPR, so the compiler has waited for the word -- on whichever counter its load counts -- before that point, and
+// no asm statement moves across it. Called before the kernel's first asm load, the hand-counted waits therefore see
+// exactly the loads they count: none is outstanding when the first of them is issued.
+constexpr int32_t kFitMinExpLo = -154, kFitMinExpHi = 133;
+template <bool WAITED>
+__device__ __forceinline__ Params fitted_params_dev(uint32_t maxprec, const int32_t* __restrict__ d_minexp)
+{
+  int m = __builtin_amdgcn_readfirstlane(min(max(*d_minexp, kFitMinExpLo), kFitMinExpHi));
+  if constexpr (WAITED) asm volatile("" : "+s"(m) : : "memory");
+  return Params{1u, 16658u, maxprec, m};
+}
+
 }  // namespace gcow

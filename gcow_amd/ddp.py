@@ -24,7 +24,9 @@ residual from its own coefficients for accuracy / precision sets, which have no 
 
 Accuracy mode under a bit budget (`GcowHookState.target_bits`, all three hooks): the tolerance is fitted to a budget
 in bits per value from the bucket's rate table (codec.rate_table: the stream length under every minexp from one pass);
-roundtrip_hook bounds the budget, the wire hooks track it with a control lagged by one step.
+roundtrip_hook bounds the budget, the wire hooks track it with a control lagged by one step -- or, with
+`GcowHookState.fit_on_device`, compressed_allgather_hook fits the very step it encodes: table, fit and encode run on
+the device back to back (codec.fit_device, codec.encode_fitted_device), and the step's streams meet the budget.
 """
 import contextlib
 import queue
@@ -107,7 +109,25 @@ class GcowHookState:
     table is taken of the bucket, not of bucket + carried error. (codec.encode_fitted and roundtrip_hook do bound
     it.) A budget below one bit per block selects the coarsest entry. `mean_params` of `compress_mean` is not fitted.
     `reset_error_feedback()` keeps the fitted values; `reset_rate_fit()` forgets them (the next step uses `params`).
-    Unset (the default): nothing changes and rate_table is never called."""
+    Unset (the default): nothing changes and rate_table is never called.
+
+    `fit_on_device` (roundtrip_hook and compressed_allgather_hook, only together with `target_bits`; ValueError
+    without it): the fit is a kernel (codec.fit_device) and the encode or round trip takes minexp from the 16-byte
+    record it writes (codec.encode_fitted_device / roundtrip_fitted), so nothing is read on the host between the table
+    pass and the coder. roundtrip_hook: the `then` callback launches table -> fit -> round trip in place and returns;
+    no `.cpu()`, `_fits` is not updated, `fit_record(index)` is the device record. compressed_allgather_hook: the
+    encode moves from the autograd thread into the exchange, on the side stream: this step's table, its all-reduce
+    over the exchange group (world > 1), the fit against world * floor(target_bits * n) bits, the encode under that
+    fit and the index packing; the record is read on the host right after the gathered lengths, where the comm thread
+    has just waited anyway, and the decode runs under fitted_params(maxprec, minexp). Every rank fits the same summed
+    table, so every rank codes under the same set, and the W streams of THIS step total at most
+    world * floor(target_bits * n) bits -- the budget is bounded, not tracked, and step 1 is fitted like every other.
+    A budget below one bit per block cannot be met: the record's status is 1 and the coarsest set (minexp 133) is
+    used, as the lagged control does. The price is latency: table, all-reduce (2.3 KB) and fit now run before the
+    encode instead of beside it, and the encode no longer overlaps the autograd thread's work. Combined with
+    `error_feedback` or `compress_mean`, or registered with compressed_sharded_hook: ValueError -- those encodes are
+    other kernel families. A codec without rate_table, fit_device, encode_fitted and
+    roundtrip_fitted: ValueError. Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -124,6 +144,9 @@ class GcowHookState:
     relative_bits: int | None = None
     # accuracy mode under a budget of this many bits per value (class docstring)
     target_bits: float | None = None
+    # with target_bits: fit on the device, in the step that is encoded (class docstring)
+    fit_on_device: bool = False
+    _fit_records: dict = field(default_factory=dict, repr=False)  # bucket index -> the device gcow_fit record
     _fits: dict = field(default_factory=dict, repr=False)  # bucket index -> (numel, fitted minexp)
     _worker: object = field(default=None, repr=False)
     _side: dict = field(default_factory=dict, repr=False)
@@ -206,6 +229,8 @@ class GcowHookState:
     def check_target(self):
         """ValueError for a `target_bits` the hooks cannot serve (class docstring); nothing when it is unset."""
         if self.target_bits is None:
+            if self.fit_on_device:
+                raise ValueError("fit_on_device fits target_bits on the device: set target_bits")
             return
         if not _codec.is_nobudget(self.params) or _codec.is_fixed(self.params):
             raise ValueError("target_bits fits accuracy mode: params must be a variable-rate set without a block "
@@ -224,6 +249,31 @@ class GcowHookState:
     def reset_rate_fit(self):
         """Forget every fitted minexp (target_bits): the next step codes under `params` again."""
         self._fits.clear()
+        self._fit_records.clear()
+
+    def fit_record(self, index):
+        """fit_on_device: the gcow_fit record of bucket `index`'s latest step, on the bucket's device (None before its
+        first step); codec.read_fit reads it on the host."""
+        return self._fit_records.get(index)
+
+    def check_fit_on_device(self, cdc, hook_name: str) -> bool:
+        """-> fit_on_device, after ValueError for what the mode cannot be combined with (class docstring)."""
+        if not self.fit_on_device:
+            return False
+        why = None
+        if self.error_feedback:
+            why = "error_feedback encodes with the residual form, another kernel family"
+        elif self.compress_mean:
+            why = "compress_mean encodes the mean with the reduce encoder, another kernel family"
+        elif hook_name == "compressed_sharded_hook":
+            why = "compressed_sharded_hook decodes the pieces it receives under host parameters in the same exchange"
+        if why:
+            raise ValueError("fit_on_device is for roundtrip_hook and compressed_allgather_hook without error "
+                             "feedback: " + why)
+        missing = [m for m in ("rate_table", "fit_device", "encode_fitted", "roundtrip_fitted") if not hasattr(cdc, m)]
+        if missing:
+            raise ValueError("fit_on_device needs a codec with %s (gcow_amd.dist.DeviceCodec)" % ", ".join(missing))
+        return True
 
     def side_stream(self, dev):
         if dev not in self._side:
@@ -314,6 +364,7 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
     group = state.process_group
     buf = bucket.buffer()
     cdc = state.get_codec()
+    fod = state.check_fit_on_device(cdc, "roundtrip_hook")
     rel = state.relative_bits
     if rel is not None:
         if not hasattr(cdc, "roundtrip_relative"):
@@ -332,6 +383,14 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
         flat, x = _flat(t)
         p = state.params
         bidx = bucket.index() if hasattr(bucket, "index") else None
+        if fod:  # table -> fit -> round trip under the record, all on the device: nothing is read here
+            rec = cdc.fit_device(_rate_table(state, cdc, x, bidx), _budget(state, x.numel()), slot=("fit", bidx))
+            state._fit_records[bidx] = rec
+            direct = flat.dtype in (torch.float32, torch.bfloat16) and flat.is_contiguous()
+            cdc.roundtrip_fitted(x, rec, p.maxprec, out=flat if direct else x)
+            if not direct:
+                flat.copy_(x.to(flat.dtype))
+            return t
         if state.target_bits is not None:  # the reduced bucket's own table: the same fit on every rank
             table = _rate_table(state, cdc, x, bidx)
             me, _ = _codec.fit_minexp(table, _budget(state, x.numel()))  # host read, in this callback
@@ -412,12 +471,13 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
     state.check_target()
+    cdc = state.get_codec()
+    fod = state.check_fit_on_device(cdc, "compressed_allgather_hook")  # before any collective
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
     flat, x = _flat(buf)
     n = x.numel()
-    cdc = state.get_codec()
     slot = bucket.index() if hasattr(bucket, "index") else None
     p = state.step_params(slot, n)  # state.params, or with target_bits the set fitted in the step before
     if _codec.is_fixed(p):
@@ -437,9 +497,12 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
 
         return fut.then(finish)
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot, p)
-    index = cdc.pack_index16(index8, n, p)  # what travels: one entry per 16 blocks
-    table = _rate_table(state, cdc, x, slot)  # target_bits: this step's lengths, for the next step's set
+    if fod:  # encoded inside the exchange, under this step's own fit
+        words = bits = index = table = None
+    else:
+        words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot, p)
+        index = cdc.pack_index16(index8, n, p)  # what travels: one entry per 16 blocks
+        table = _rate_table(state, cdc, x, slot)  # target_bits: this step's lengths, for the next step's set
     dev = x.device
     if dev.type == "cuda":
         ev = torch.cuda.Event()
@@ -451,18 +514,30 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
         fut = torch.futures.Future()
 
     def exchange(fut):
+        nonlocal words, bits, index, p
         if side is not None:
             torch.cuda.set_device(dev)  # this thread's current device: the bucket's, on every LOCAL_RANK
         ctx = torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
         with ctx:
             if side is not None:
                 side.wait_event(ev)
-                for t in (words, bits, index, table):  # read on the side stream: kept from the allocator until then
-                    if t is not None:
+                for t in (words, bits, index, table, x if fod else None):  # read on the side stream: kept from the
+                    if t is not None:                                      # allocator until then
                         t.record_stream(side)
-            if table is not None:
+            rec = None
+            if fod:  # this step's table, summed over the ranks, fitted and encoded under on the device
+                tab = _rate_table(state, cdc, x, slot)
+                if world > 1:
+                    dist.all_reduce(tab, group=cgroup)
+                rec = cdc.fit_device(tab, world * _budget(state, n), slot=("fit", slot))
+                state._fit_records[slot] = rec
+                words, bits, index8 = cdc.encode_fitted(x, rec, p.maxprec, SHARDED_INDEX_STRIDE, slot=slot)
+                index = cdc.pack_index16(index8, n, p)  # the packing reads no minexp
+            elif table is not None:
                 _fit_next(state, table, slot, n, world, cgroup)
             lens, lens_h = gdist.gather_lengths(bits, dev, cgroup)  # host read: this thread waits, autograd does not
+            if rec is not None:  # the stream has just drained: 16 bytes more, no new wait
+                p = _codec.fitted_params(p.maxprec, _codec.read_fit(rec)[0])
             maxw = max(1, max((b + 63) // 64 for b in lens_h))
             rank = dist.get_rank(cgroup)
             gathered = gdist.allgather_padded(words, (lens_h[rank] + 63) // 64, maxw, cgroup, pad=2)
@@ -518,6 +593,7 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
     state.check_target()
+    state.check_fit_on_device(state.get_codec(), "compressed_sharded_hook")
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)

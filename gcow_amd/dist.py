@@ -152,6 +152,44 @@ class DeviceCodec:
         self._evict_idle()
         return ent[0](x if x.is_contiguous() else x.contiguous(), maxprec)
 
+    def _cached(self, key, make):
+        self._tick += 1
+        ent = self._enc.get(key)
+        if ent is None:
+            ent = self._enc[key] = [make(), self._tick]
+        else:
+            ent[1] = self._tick
+            self._enc.move_to_end(key)
+        self._evict_idle()
+        return ent[0]
+
+    def fit_device(self, table: torch.Tensor, budget_bits: int, slot=None) -> torch.Tensor:
+        """The fit of a device rate table against budget_bits, on the device (codec.fit_device): -> the gcow_fit
+        record, int64[2] on the table's device (codec.read_fit reads it on the host). No host read. The record is
+        cached per (slot, device) under the encoders' idleness rule; calls with the same key overwrite one record."""
+        from . import codec
+        rec = self._cached((slot, table.device, "fit"), lambda: codec.new_fit_record(table.device))
+        return codec.fit_device(table, budget_bits, out=rec)
+
+    def encode_fitted(self, x: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64, index_stride: int = 0,
+                      slot=None):
+        """`encode` under expert(1, 16658, maxprec, minexp) with minexp read on the device from minexp_word (a
+        fit_device record) when the kernels run (codec.encode_fitted_device): -> (words, bits, index). Output buffers
+        cached per slot like the encoders', apart from theirs."""
+        from . import codec
+        x = x.reshape(-1)
+        key = (slot, x.numel(), x.dtype, x.device, int(maxprec), index_stride, "fitted")
+        enc = self._cached(key, lambda: codec.Encoder((x.numel(),), x.dtype, codec.fitted_params(maxprec, 0),
+                                                      x.device, index_stride))
+        e = codec._encode_fitted_into(enc, x if x.is_contiguous() else x.contiguous(), minexp_word)
+        return e.words, e.bits_dev, e.index
+
+    def roundtrip_fitted(self, x: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64, out=None):
+        """`roundtrip` under the set minexp_word stands for, read on the device (codec.roundtrip_fitted): nothing
+        cached, nothing allocated when `out` is given (out=x: in place)."""
+        from . import codec
+        return codec.roundtrip_fitted(x, minexp_word, maxprec, out=out)
+
     def pack_index16(self, index8, n: int, params):
         from . import codec
         return codec.pack_index16(index8, n, params)

@@ -476,6 +476,55 @@ gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uin
 gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, int* minexp, uint64_t* bits);
 
 /*
+ * The fit on the device, and encode / round trip under a minexp that lives in device memory: table, fit and encode (or
+ * round trip) are launched back to back on one stream with no host read in between, and can be captured into one graph
+ * that follows the data it is replayed on.
+ *
+ * gcow_rate_table_fit_device: d_table holds 288 DEVICE entries as gcow_rate_table_device writes them, or a sum of
+ * several fields' tables (the ranks of an exchange: the length of all their streams under each minexp). One workgroup
+ * writes *d_fit (DEVICE, 8-byte aligned) = what gcow_rate_table_fit returns on a host copy of the table: the smallest
+ * minexp in [-154, 133] whose entry is <= budget_bits, that entry in bits, status = 0. Where the host call fails
+ * (budget_bits below entry 287) the device call cannot: it writes minexp = 133, bits = d_table[287], status = 1 -- the
+ * coarsest set, for the caller to accept or refuse when it next reads the record. The 16 bytes of the record are
+ * written with ordinary stores and nothing past them. No allocation, no synchronisation; legal inside a stream
+ * capture. GCOW_ERR_INVALID: a NULL or misaligned (8 bytes) d_table or d_fit.
+ *
+ * gcow_encode_fitted_device: field is 1-D, contiguous, dtype_float or dtype_bf16, at any element-aligned address.
+ * With m = clamp(*d_minexp, -154, 133), the word read ON THE DEVICE when the kernels run, every output is byte for
+ * byte what gcow_encode_device(field, {1, 16658, maxprec, m}, ...) writes with the same arguments: the stream,
+ * *d_total_bits, the index at index_stride, the zeroed flush word, and nothing else. The clamp loses nothing: the rate
+ * table's range is complete (above), below -154 and from 132 on the stream no longer changes; it keeps emax - minexp
+ * inside int for any input word. d_minexp: any 4-byte aligned DEVICE word, unchanged by the call; the first word of a
+ * gcow_fit is the intended source. out_capacity and the workspace are gcow_max_output_bytes / gcow_encode_workspace_bytes
+ * of {1, 16658, maxprec, any minexp}: NEITHER DEPENDS ON minexp, so both can be sized before the fit exists. Always the
+ * tile form of the 1-D variable-rate encoder: gcow_debug_set_var1d_variant does not apply. nx = 0 writes
+ * *d_total_bits = 0. GCOW_ERR_UNSUPPORTED: dims != 1, a non-unit stride, a dtype other than float / bf16.
+ * GCOW_ERR_INVALID: NULL field or d_out, a NULL or misaligned d_minexp, field->data misaligned for its element type,
+ * d_out / d_total_bits / d_index / d_workspace off 8 bytes, a bad index_stride, a workspace below the query.
+ * GCOW_ERR_CAPACITY: out_capacity below the bound.
+ *
+ * gcow_roundtrip_fitted_device: the same relation to gcow_roundtrip_device under {1, 16658, maxprec, m}: d_out and
+ * *d_total_bits bit for bit. dtype_float / dtype_bf16 in and out in any combination; d_out == field->data is allowed
+ * when the dtypes are equal. Buffers off 16-byte alignment and the partial last block go through the generic kernel
+ * under the same device word. Errors as gcow_roundtrip_device's, and GCOW_ERR_INVALID for a NULL or misaligned d_minexp.
+ *
+ * Decoders are untouched: a stream is decoded under host parameters. A caller that needs minexp on the host reads the
+ * 16-byte record when it next has to wait anyway.
+ */
+typedef struct {
+  int32_t minexp;   /* the fitted minexp, GCOW_RATE_TABLE_MINEXP_LO .. + GCOW_RATE_TABLE_ENTRIES - 1 */
+  uint32_t status;  /* 0: bits <= budget_bits; 1: no entry fits, the coarsest set was taken */
+  uint64_t bits;    /* the table entry at minexp */
+} gcow_fit;         /* 16 bytes, 8-byte aligned */
+gcow_status gcow_rate_table_fit_device(const uint64_t* d_table, uint64_t budget_bits, gcow_fit* d_fit, void* hip_stream);
+gcow_status gcow_encode_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp, void* d_out,
+                                      size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                      size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                      void* hip_stream);
+gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp, void* d_out,
+                                         data_type out_dtype, uint64_t* d_total_bits, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by

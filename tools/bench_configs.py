@@ -11,6 +11,8 @@
   var_decode  256 Mi fp32 1-D accuracy 1e-6 / 1e-3 decode (block index every 16 blocks)
   rate_table  256 Mi fp32 / bf16 1-D: the rate-table pass against the accuracy-1e-3 encode, and the fitted encode end
               to end (interleaved rounds in one process)
+  fit_device  256 Mi fp32 / bf16 1-D at 4 and 8 bits per value: encode and round trip with minexp from device memory
+              against the host-parameter calls, and codec.FittedEncoder against table + host fit + encode
 Timing: HIP events on the launching stream, median of interleaved rounds.
 """
 import argparse
@@ -266,6 +268,63 @@ def rate_table(bits_per_value=8.0):
     for _ in range(3):
         codec.encode_fitted(x, bits_per_value)[0].bits
     emit(case="rate_table_encode_fitted_oneshot", ms=round((time.perf_counter() - t0) * 1e3 / 3, 3))
+
+
+def fit_device():
+    """The fit on the device, 256 Mi values, fp32 and bf16, at 4 and 8 bits per value, interleaved rounds in one
+    process. Per config, after the two forms were checked to leave the same bits:
+      (a) gcow_encode_fitted_device alone (minexp from a device word) against gcow_encode_device under the same set,
+          the latter twice (its own run-to-run spread);
+      (b) the whole FittedEncoder call (table + device fit + encode, no host read) against table + host fit + encode
+          (the 2.3 KB read; preallocated, as `rate_table` above times it), both by the host clock to a synchronise;
+      (c) gcow_roundtrip_fitted_device against gcow_roundtrip_device under the same set, the latter twice."""
+    n = 256 << 20
+    x32 = torch.empty(n, dtype=torch.float32, device="cuda")
+    codec.fill_normal(x32)
+    for dt, x in (("f32", x32), ("bf16", x32.to(torch.bfloat16))):
+        rt = codec.RateTable(n, x.dtype)
+        out = torch.empty_like(x)
+        for bpv in (4.0, 8.0):
+            budget = int(bpv * n)
+            me, fit_bits = codec.fit_minexp(rt(x), budget)
+            pf = codec.fitted_params(64, me)
+            enc_host = codec.Encoder((n,), x.dtype, pf)
+            enc_dev = codec.Encoder((n,), x.dtype, codec.fitted_params(64, 0))
+            word = torch.tensor([me], dtype=torch.int32, device="cuda")
+            fe = codec.FittedEncoder(n, x.dtype, bpv)
+
+            def host_fitted():
+                m, _ = codec.fit_minexp(rt(x), budget)  # the host read
+                assert m == me
+                return enc_host(x)
+
+            a, b, c = enc_host(x), codec._encode_fitted_into(enc_dev, x, word), fe(x)
+            nw = (fit_bits + 63) // 64
+            assert a.bits == b.bits == c.bits == fit_bits and codec.read_fit(fe.fit) == (me, 0, fit_bits)
+            assert torch.equal(a.words[:nw], b.words[:nw]) and torch.equal(a.words[:nw], c.words[:nw])
+            r0 = codec.roundtrip(x, pf)
+            assert torch.equal(codec.roundtrip_fitted(x, word, out=out).view(torch.int16), r0.view(torch.int16))
+            del r0
+            fns = {"a_encode_host_params": lambda: enc_host(x),
+                   "a_encode_fitted": lambda: codec._encode_fitted_into(enc_dev, x, word),
+                   "a_encode_host_params_again": lambda: enc_host(x),
+                   "b_table_hostfit_encode": host_fitted, "b_fitted_encoder": lambda: fe(x),
+                   "c_roundtrip_host_params": lambda: codec.roundtrip(x, pf, out=out),
+                   "c_roundtrip_fitted": lambda: codec.roundtrip_fitted(x, word, out=out),
+                   "c_roundtrip_host_params_again": lambda: codec.roundtrip(x, pf, out=out)}
+            med, span = timeit_interleaved(fns, host=("b_table_hostfit_encode", "b_fitted_encoder"))
+            for k in fns:
+                emit(case="fit_device_%s_%gbpv_%s" % (dt, bpv, k), ms=round(med[k], 4), ms_min=round(span[k][0], 4),
+                     ms_max=round(span[k][1], 4))
+            emit(case="fit_device_%s_%gbpv_summary" % (dt, bpv), fitted_minexp=me,
+                 fitted_bits_per_value=round(fit_bits / n, 4),
+                 a_fitted_minus_host_ms=round(med["a_encode_fitted"] - med["a_encode_host_params"], 4),
+                 a_host_spread_ms=round(abs(med["a_encode_host_params_again"] - med["a_encode_host_params"]), 4),
+                 b_fitted_minus_host_ms=round(med["b_fitted_encoder"] - med["b_table_hostfit_encode"], 4),
+                 c_fitted_minus_host_ms=round(med["c_roundtrip_fitted"] - med["c_roundtrip_host_params"], 4),
+                 c_host_spread_ms=round(abs(med["c_roundtrip_host_params_again"] - med["c_roundtrip_host_params"]),
+                                        4))
+            del enc_host, enc_dev, fe, a, b, c
 
 
 if __name__ == "__main__":
