@@ -598,15 +598,27 @@ class RateTable:
         self.ws = torch.empty(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
         self.table = torch.empty(RATE_TABLE_ENTRIES, dtype=torch.int64, device=self.device)
 
-    def __call__(self, x: torch.Tensor, maxprec: int = 64, stream=None) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, maxprec: int = 64, stream=None,
+                 err: torch.Tensor | None = None) -> torch.Tensor:
+        """With `err` (fp32, n values): the table of y = x.float() + err, the array encode_residual codes, formed in
+        registers (gcow_rate_table_residual_device)."""
         if x.dim() != 1 or x.numel() != self.n or x.dtype != self.dtype:
             raise GcowError("RateTable built for %d %s values, got %s %s" % (self.n, self.dtype, tuple(x.shape),
                                                                             x.dtype))
         if not (x.is_cuda and x.is_contiguous()):
             raise GcowError("rate_table expects a contiguous 1-D device tensor")
         f = field_of(x) if self.n else field_of_shape((0,), self.dtype)
-        check(self.L.gcow_rate_table_device(C.byref(f), int(maxprec), self.table.data_ptr(), self.ws.data_ptr(),
-                                            self.ws_bytes, _stream_ptr(stream)), "gcow_rate_table_device")
+        if err is None:
+            check(self.L.gcow_rate_table_device(C.byref(f), int(maxprec), self.table.data_ptr(), self.ws.data_ptr(),
+                                                self.ws_bytes, _stream_ptr(stream)), "gcow_rate_table_device")
+            return self.table
+        if not (err.is_cuda and err.device == x.device and err.dtype == torch.float32 and err.is_contiguous()
+                and err.numel() == self.n):
+            raise GcowError("rate_table_residual: err must be a contiguous fp32 tensor of x.numel() values on x's "
+                            "device")
+        check(self.L.gcow_rate_table_residual_device(C.byref(f), err.data_ptr() if self.n else None, int(maxprec),
+                                                     self.table.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                                     _stream_ptr(stream)), "gcow_rate_table_residual_device")
         return self.table
 
 
@@ -616,6 +628,15 @@ def rate_table(x: torch.Tensor, maxprec: int = 64, stream=None) -> torch.Tensor:
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise GcowError("dtype %s not supported (float32, bfloat16)" % x.dtype)
     return RateTable(x.numel(), x.dtype, x.device)(x, maxprec, stream)
+
+
+def rate_table_residual(x: torch.Tensor, err: torch.Tensor | None, maxprec: int = 64, stream=None) -> torch.Tensor:
+    """The rate table of y = x.float() + err (err: fp32 device tensor of x.numel() values, or None for zeros): entry t
+    is the bit count codec.encode_residual(x, err, expert(1, 16658, maxprec, -154 + t)) reports. One pass over x and
+    err; y is never written to memory."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("dtype %s not supported (float32, bfloat16)" % x.dtype)
+    return RateTable(x.numel(), x.dtype, x.device)(x, maxprec, stream, err)
 
 
 def fit_minexp(table, budget_bits: int):
@@ -763,6 +784,63 @@ def encode_fitted_device(x: torch.Tensor, minexp_word: torch.Tensor, maxprec: in
         raise GcowError("encode_fitted_device expects a device tensor")
     enc = Encoder((x.numel(),), x.dtype, fitted_params(maxprec, 0), x.device, index_stride)
     return _encode_fitted_into(enc, x, minexp_word, stream)
+
+
+def _encode_residual_fitted_into(enc: Encoder, x: torch.Tensor, err: torch.Tensor, minexp_word: torch.Tensor,
+                                 stream=None) -> Encoded:
+    if x.dim() != 1 or tuple(x.shape) != enc.shape:
+        raise GcowError("fitted residual encoder built for %s, got %s" % (enc.shape, tuple(x.shape)))
+    _check_err(x, err)
+    f = field_of(x) if x.numel() else field_of_shape((0,), x.dtype)
+    st = enc.L.gcow_encode_residual_fitted_device(C.byref(f), enc.params.maxprec, _minexp_ptr(minexp_word, x.device),
+                                                  err.data_ptr(), err.data_ptr(), enc.words.data_ptr(), enc.cap,
+                                                  enc.bits_dev.data_ptr(), enc.ws.data_ptr(), enc.ws_bytes,
+                                                  enc.index.data_ptr() if enc.index is not None else None,
+                                                  enc.index_stride, _stream_ptr(stream))
+    check(st, "gcow_encode_residual_fitted_device")
+    return Encoded(enc.words, enc.bits_dev, enc.shape, None, enc.index, enc.index_stride)
+
+
+def encode_residual_fitted_device(x: torch.Tensor, err: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64,
+                                  index_stride: int = 0, stream=None) -> Encoded:
+    """gcow_encode_residual_fitted_device: error feedback under a minexp word in device memory. y = x + err (x:
+    contiguous 1-D device tensor, fp32 / bf16; err: fp32, updated in place) is encoded under
+    expert(1, 16658, maxprec, clamp(minexp_word[0], -154, 133)), the word (an int32 device tensor, or a gcow_fit record
+    from fit_device) read on the device when the kernels run. Stream, bits, index and err are byte for byte
+    codec.encode_residual's under that set. x and err must be 16-byte aligned (GcowError otherwise: there is no
+    composed fallback). The returned Encoded has params None."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise GcowError("dtype %s not supported (float32, bfloat16)" % x.dtype)
+    if not x.is_cuda:
+        raise GcowError("encode_residual_fitted_device expects a device tensor")
+    # capacity and workspace are those of the fp32 field y, and do not depend on minexp
+    enc = Encoder((x.numel(),), torch.float32, fitted_params(maxprec, 0), x.device, index_stride)
+    return _encode_residual_fitted_into(enc, x, err, minexp_word, stream)
+
+
+class FittedResidualEncoder:
+    """Error feedback under a bit budget with no host read: FittedEncoder for y = x + err. Calling it with (x, err)
+    launches the rate table of y (formed in registers, gcow_rate_table_residual_device), the device fit against
+    floor(bits_per_value * n) bits and gcow_encode_residual_fitted_device, which codes y under the fitted set and
+    leaves err = finite(y - decode(stream)). The budget therefore holds for what is encoded, y, not for x alone.
+    Everything is preallocated: the three launches allocate and synchronise nothing and capture into one graph.
+    `fit`, `params()` as FittedEncoder's."""
+
+    def __init__(self, n: int, dtype, bits_per_value: float, maxprec: int = 64, device=None, index_stride: int = 0):
+        self.n, self.dtype, self.maxprec = int(n), dtype, int(maxprec)
+        self.device = torch.device(device or "cuda")
+        self.budget = int(math.floor(bits_per_value * self.n))
+        self.table = RateTable(self.n, dtype, self.device)
+        self.fit = new_fit_record(self.device)
+        self.enc = Encoder((self.n,), torch.float32, fitted_params(self.maxprec, 0), self.device, index_stride)
+        self.L = self.enc.L
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor, stream=None) -> Encoded:
+        self.table(x, self.maxprec, stream, err)  # checks x and err
+        fit_device(self.table.table, self.budget, self.fit, stream)
+        return _encode_residual_fitted_into(self.enc, x, err, self.fit, stream)
+
+    params = FittedEncoder.params
 
 
 def roundtrip_fitted(x: torch.Tensor, fit, maxprec: int = 64, out: torch.Tensor | None = None,

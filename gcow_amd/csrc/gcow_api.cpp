@@ -995,6 +995,14 @@ size_t gcow_rate_table_workspace_bytes(const zfp_input* field)
 gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uint64_t* d_table, void* d_workspace,
                                    size_t workspace_bytes, void* hip_stream)
 {
+  return gcow_rate_table_residual_device(field, nullptr, maxprec, d_table, d_workspace, workspace_bytes, hip_stream);
+}
+
+// d_err_in NULL: the table of the field itself (launch_rate_table1d_resid routes to launch_rate_table1d)
+gcow_status gcow_rate_table_residual_device(const zfp_input* field, const float* d_err_in, uint32_t maxprec,
+                                            uint64_t* d_table, void* d_workspace, size_t workspace_bytes,
+                                            void* hip_stream)
+{
   if (!field) return fail(GCOW_ERR_INVALID, "null field");
   if (field->ny || field->nz || field->nw) return fail(GCOW_ERR_INVALID, "rate_table takes 1-D fields");
   if (field->sx != 0 && field->sx != 1) return fail(GCOW_ERR_INVALID, "rate_table takes contiguous fields");
@@ -1010,10 +1018,11 @@ gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uin
   if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
   if ((uintptr_t)field->data % (field->dtype == dtype_bf16 ? 2 : 4))
     return fail(GCOW_ERR_INVALID, "buffer misaligned for its element type");
+  if ((uintptr_t)d_err_in % 4) return fail(GCOW_ERR_INVALID, "misaligned error buffer");
   gcow::FieldDesc F;
   gcow_status st = make_field(field, F, false);
   if (st) return st;
-  GCOW_HIP(gcow::launch_rate_table1d(F, maxprec, d_table, (uint64_t*)d_workspace, hip_stream));
+  GCOW_HIP(gcow::launch_rate_table1d_resid(F, d_err_in, maxprec, d_table, (uint64_t*)d_workspace, hip_stream));
   return GCOW_OK;
 }
 
@@ -1091,6 +1100,50 @@ gcow_status gcow_encode_fitted_device(const zfp_input* field, uint32_t maxprec, 
     return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_workspace_bytes()");
   GCOW_HIP(gcow::launch_encode1d_var_tile_fitted(F, maxprec, d_minexp, (uint32_t*)d_out, (uint64_t*)d_workspace,
                                                  d_total_bits, d_index, shift, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_encode_residual_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp,
+                                               const float* d_err_in, float* d_err_out, void* d_out,
+                                               size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                               size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                               void* hip_stream)
+{
+  gcow_status st = fitted_field(field, d_minexp, "encode_residual_fitted");
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!d_err_out) return fail(GCOW_ERR_INVALID, "null d_err_out");
+  if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+  if ((uintptr_t)d_total_bits % 8 || (uintptr_t)d_index % 8 || (uintptr_t)d_workspace % 8 || (uintptr_t)d_out % 8)
+    return fail(GCOW_ERR_INVALID, "misaligned output, d_total_bits, d_index or workspace");
+  uint32_t shift = 0;
+  if (d_index) {
+    if (!index_stride || index_stride > 256 || (index_stride & (index_stride - 1)))
+      return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+    while ((1u << shift) < index_stride) shift++;
+  }
+  if (field->nx == 0) {
+    if (d_total_bits) GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+    return GCOW_OK;
+  }
+  if (!field->data) return fail(GCOW_ERR_INVALID, "null field data");
+  // the tile form only: no composed fallback, whose decoder would need minexp on the host
+  if (((uintptr_t)field->data | (uintptr_t)d_err_in | (uintptr_t)d_err_out) % 16)
+    return fail(GCOW_ERR_UNSUPPORTED, "encode_residual_fitted takes 16-byte aligned field data and error buffers");
+  gcow::FieldDesc F;
+  if ((st = make_field(field, F, false))) return st;
+  zfp_input yf;  // the fp32 field of y: the sizes are its, whatever x's dtype
+  std::memset(&yf, 0, sizeof(yf));
+  yf.dtype = dtype_float;
+  yf.nx = field->nx;
+  if (out_capacity < gcow_max_output_bytes(&yf, &hp))
+    return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_max_output_bytes()");
+  if (!d_workspace || workspace_bytes < gcow_encode_workspace_bytes(&yf, &hp))
+    return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_workspace_bytes()");
+  GCOW_HIP(gcow::launch_encode_resid1d_var_fitted(F.data, (int)F.dtype, F.n[0], maxprec, d_minexp, d_err_in, d_err_out,
+                                                  (uint32_t*)d_out, (uint64_t*)d_workspace, d_total_bits, d_index,
+                                                  shift, hip_stream));
   return GCOW_OK;
 }
 

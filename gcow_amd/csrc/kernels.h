@@ -190,6 +190,11 @@ constexpr uint32_t kRateTableEntries = 288;
 constexpr uint32_t kRateTableTileValues = 4096;
 size_t rate_table_workspace_bytes();
 hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream);
+// The table of y = fadd(x, e_in) (x = F, fp32 / bf16 widened exactly; e_in fp32 at any 4-byte aligned address, null:
+// launch_rate_table1d), i.e. what launch_encode_resid1d_var leaves in *d_total. y is formed in registers and never
+// stored; both rows 16-byte aligned take the wide loads, else every tile is gathered. ws and table as above.
+hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint32_t maxprec, uint64_t* table,
+                                     uint64_t* ws, void* stream);
 // The fit on the device (rate_table1d.hip k_rate_table_fit; include/gcow.h gcow_fit has this layout): the smallest t
 // with table[t] <= budget -> {kRateTableMinExpLo + t, 0, table[t]}; none -> {the last entry's minexp, 1, table[287]}.
 // One workgroup of kRateTableEntries lanes; the record is written with plain stores and nothing past it.
@@ -207,6 +212,12 @@ hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, Ra
 hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
                                            uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
                                            uint32_t index_shift, void* stream);
+// launch_encode_resid1d_var under that set: the same arguments, workspace layout and outputs (stream, *d_total, index,
+// e_out; e_in null: zeros, e_in == e_out allowed); x, e_in and e_out 16-byte aligned.
+hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t nvals, uint32_t maxprec,
+                                            const int32_t* d_minexp, const float* e_in, float* e_out, uint32_t* out32,
+                                            uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
+                                            void* stream);
 // launch_roundtrip1d under that set: rows16 (in and out 16-byte aligned) selects kRoundtripVar with the generic kernel
 // for the partial last block, else kRoundtripGeneric throughout. total as launch_roundtrip1d's.
 hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nvals, uint32_t maxprec,

@@ -22,6 +22,8 @@
 //                         wave on the same few bins, and same-address LDS atomics serialise, so the copies cut a
 //                         64-deep conflict to 4. At the end the workgroup sums the copies and adds its non-zero bins
 //                         to the global workspace with 64-bit atomics (steps sign-extended).
+//   k_rate_table1d_xe     the same pass over two rows, x and a carried error e: the table of y = x + e formed in
+//                         registers (gcow_rate_table_residual_device).
 //   k_rate_table_finish   288 x 2 workspace words -> the table: both suffix sums in one backward sweep.
 //   k_rate_table_zero     the workspace zeroed in stream order ahead of the first kernel. A kernel and not a memset:
 //                         in a captured graph that also holds the fit and the encoder (FittedEncoder), the memset
@@ -188,6 +190,75 @@ __global__ __launch_bounds__(RTT) void k_rate_table1d(FieldDesc F, uint32_t pmax
   }
 }
 
+// The lane's RTU blocks of y = x + e from its x words and e words: the single fadd of the residual encoder
+// (v1_form_y, var1d.hip), a bf16 x widened exactly. y lives in registers only.
+template <int DT>
+__device__ __forceinline__ void rt_form_y(const RtRaw<DT>& rx, const RtRaw<DT_F32>& re, RtRaw<DT_F32>& y)
+{
+#pragma unroll
+  for (uint32_t k = 0; k < RTU; k++) {
+    float f[4], e[4];
+    rx.block(k, f);
+    re.block(k, e);
+    y.w[k] = make_uint4(__float_as_uint(__fadd_rn(f[0], e[0])), __float_as_uint(__fadd_rn(f[1], e[1])),
+                        __float_as_uint(__fadd_rn(f[2], e[2])), __float_as_uint(__fadd_rn(f[3], e[3])));
+  }
+}
+
+// k_rate_table1d over two input rows (gcow_rate_table_residual_device): the table of y = x + e. The same tiles,
+// grid-stride loop and next-tile prefetch, which now holds the lane's x rows (fp32: 4, bf16: 2) and its 4 e rows; the
+// blocks go through rt_tile as fp32 y, so Inf / NaN blocks of y (x + e may overflow) take the generic rule there.
+// The wide path needs both rows 16-byte aligned; else every tile is gathered, x and e with the same padding indices,
+// so a padding value of y is a copy of a real one -- the encoder's padding of y.
+template <int DT>
+__global__ __launch_bounds__(RTT) void k_rate_table1d_xe(FieldDesc F, const float* __restrict__ e_in, uint32_t pmax,
+                                                         uint32_t ntiles, unsigned long long* __restrict__ ws)
+{
+  __shared__ uint32_t hist[2 * RT_BINS * RT_COPIES];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < 2 * RT_BINS * RT_COPIES; i += RTT) hist[i] = 0u;
+  __syncthreads();
+  uint32_t* step = hist;
+  uint32_t* imp = hist + RT_BINS * RT_COPIES;
+  const uint32_t copy = tid & (RT_COPIES - 1u);
+  FieldDesc Fe = F;
+  Fe.data = e_in;
+  Fe.dtype = DT_F32;
+  Fe.vec = (((uintptr_t)e_in) & 15u) == 0 ? 1u : 0u;
+  const bool wide_ok = F.vec && (((uintptr_t)F.data) & 15u) == 0 && Fe.vec;
+  const uint32_t nfull = wide_ok ? (uint32_t)(F.n[0] / 4 / RT_TILE) : 0u;  // tiles of whole blocks, loaded wide
+  RtRaw<DT> curx{}, nxtx{};
+  RtRaw<DT_F32> cure{}, nxte{};
+  uint32_t t = blockIdx.x;
+  if (t < nfull) {
+    curx.load_wide(F, t);
+    cure.load_wide(Fe, t);
+  }
+  for (; t < ntiles; t += gridDim.x) {
+    if (t >= nfull) {
+      curx.gather(F, t);
+      cure.gather(Fe, t);
+    }
+    const uint32_t tn = t + gridDim.x;  // < 2^22 + 2^10
+    if (tn < nfull) {
+      nxtx.load_wide(F, tn);
+      nxte.load_wide(Fe, tn);
+    }
+    RtRaw<DT_F32> y;
+    rt_form_y<DT>(curx, cure, y);
+    rt_tile<DT_F32>(F, y, t, pmax, step, imp, copy);
+    curx = nxtx;
+    cure = nxte;
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < 2 * RT_BINS; i += RTT) {
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < RT_COPIES; c++) s += hist[i * RT_COPIES + c];
+    if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
+  }
+}
+
 __global__ __launch_bounds__(RT_BINS) void k_rate_table_zero(unsigned long long* __restrict__ ws)
 {
   ws[threadIdx.x] = 0ull;
@@ -256,6 +327,27 @@ hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* t
     const uint32_t grid = std::min(ntiles, RT_MAXGRID);
     if (F.dtype == DT_BF16) k_rate_table1d<DT_BF16><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
     else k_rate_table1d<DT_F32><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  k_rate_table_finish<<<1, RT_BINS, 0, st>>>((const unsigned long long*)ws, F.nblocks, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint32_t maxprec, uint64_t* table,
+                                     uint64_t* ws, void* stream)
+{
+  if (!e_in) return launch_rate_table1d(F, maxprec, table, ws, stream);  // y = x + 0 codes as x
+  hipStream_t st = (hipStream_t)stream;
+  k_rate_table_zero<<<1, RT_BINS, 0, st>>>((unsigned long long*)ws);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const uint32_t pmax = std::min(maxprec, 32u);
+  if (F.nblocks && pmax) {
+    const uint32_t ntiles = (uint32_t)(((uint64_t)F.nblocks + RT_TILE - 1) / RT_TILE);
+    const uint32_t grid = std::min(ntiles, RT_MAXGRID);
+    if (F.dtype == DT_BF16)
+      k_rate_table1d_xe<DT_BF16><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, (unsigned long long*)ws);
+    else k_rate_table1d_xe<DT_F32><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, (unsigned long long*)ws);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   k_rate_table_finish<<<1, RT_BINS, 0, st>>>((const unsigned long long*)ws, F.nblocks, table);

@@ -1562,4 +1562,230 @@ hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec,
   return launch_fitted1d_t<DT_F32>(F, maxprec, d_minexp, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------- tile form with the residual, minexp from device memory
+// gcow_encode_residual_fitted_device (include/gcow.h): the residual tile form under
+// Params{1, 16658, maxprec, clamp(*d_minexp)}, as the kernels above are the tile form's. Each kernel builds its Params
+// at the top and runs the residual device functions (v1_form_y, v1_load_y, v1_tile_resid, V1ResidOut) unchanged.
+//   k_count1d_var_tile_resid_fitted      k_count1d_var_tile_resid's body; the word is loaded and waited for before the
+//                                        ring's first raw buffer load (fitted_params_dev<true>), so the hand-counted
+//                                        vmcnt of v1_wait_tiles_xe holds as it stands.
+//   k_encode1d_var_tile_resid_fitted     k_encode1d_var_tile_resid: the word's load goes out with the tile's others.
+//   k_encode1d_var_tile_big_resid_fitted the oversized tiles.
+template <int DT_X, bool HASE>
+__global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid_fitted(FieldDesc F, uint32_t maxprec,
+                                                                       const int32_t* __restrict__ d_minexp,
+                                                                       const float* e_in, uint32_t ntiles,
+                                                                       uint64_t* __restrict__ sums,
+                                                                       uint32_t* __restrict__ lens8,
+                                                                       uint32_t* __restrict__ nover,
+                                                                       uint64_t* __restrict__ gsums)
+{
+  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
+  const Params p = fitted_params_dev<true>(maxprec, d_minexp);  // loaded and waited for: nothing outstanding here
+  // k_count1d_var_tile_resid's loop and its load count per tile (NT = NX + V1U with e, NX without)
+  __shared__ uint32_t red[V1CT][V1T / 64];
+  const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
+  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of the encode kernel starts empty
+  const bool wide_ok = F.vec && v1_aligned16(F.data) && (!HASE || v1_aligned16(e_in));
+  constexpr int NX = V1Raw<DT_X>::N;                                  // 16-byte x loads per lane per tile
+  constexpr uint32_t TBX = V1TILE * (DT_X == DT_BF16 ? 8u : 16u);     // x bytes per tile
+  constexpr uint32_t TBE = V1TILE * 16u;                              // e bytes per tile
+  uint32_t packed[V1CT];
+  if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
+    const v1_v4i rsx = v1_rsrc((const char*)F.data + (size_t)t0 * TBX, V1CT * TBX);
+    const v1_v4i rse = v1_rsrc((const char*)e_in + (size_t)t0 * TBE, HASE ? V1CT * TBE : 0u);
+    constexpr uint32_t PF = V1_RESID_PF, RING = PF + 1;
+    v1_u4 bx[RING][NX], be[HASE ? RING : 1][V1U];
+    auto request = [&](uint32_t i) {
+#pragma unroll
+      for (int h = 0; h < NX; h++) bx[i % RING][h] = v1_ld16(i * TBX + (tid * NX + h) * 16u, rsx);
+      if constexpr (HASE) {
+#pragma unroll
+        for (uint32_t h = 0; h < V1U; h++) be[i % RING][h] = v1_ld16(i * TBE + (tid * V1U + h) * 16u, rse);
+      }
+    };
+#pragma unroll
+    for (uint32_t i = 0; i < PF && i < V1CT; i++) request(i);
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      if (i + PF < V1CT) request(i + PF);
+      v1_wait_tiles_xe<NX, HASE>(bx[i % RING], be[HASE ? i % RING : 0], (i + PF < V1CT ? PF : V1CT - 1 - i));
+      V1Raw<DT_X> rx;
+      V1Raw<DT_F32> re, y;
+#pragma unroll
+      for (int h = 0; h < NX; h++) {
+        const v1_u4 v = bx[i % RING][h];
+        rx.w[h] = make_uint4(v.x, v.y, v.z, v.w);
+      }
+#pragma unroll
+      for (uint32_t h = 0; h < V1U; h++) {
+        if constexpr (HASE) {
+          const v1_u4 v = be[i % RING][h];
+          re.w[h] = make_uint4(v.x, v.y, v.z, v.w);
+        } else {
+          re.w[h] = make_uint4(0u, 0u, 0u, 0u);
+        }
+      }
+      v1_form_y<DT_X>(rx, re, y);
+      uint32_t lsum;
+      packed[i] = v1_count_tile<DT_F32, true>(F, p, y, t0 + i, lsum);
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  } else {  // partial tiles, the padded last block, n % 4 != 0
+#pragma unroll
+    for (uint32_t i = 0; i < V1CT; i++) {
+      uint32_t lsum = 0;
+      packed[i] = 0;
+      if (t0 + i < ntiles) {
+        V1Raw<DT_F32> y;
+        v1_load_y<DT_X>(F, HASE ? e_in : nullptr, t0 + i, y);
+        packed[i] = v1_count_tile<DT_F32>(F, p, y, t0 + i, lsum);
+      }
+      lsum = wave_sum_dpp(lsum);
+      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
+    }
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < V1CT; i++)
+    if (t0 + i < ntiles) lens8[(size_t)(t0 + i) * V1T + tid] = packed[i];
+  __syncthreads();
+  if (tid < 64) {  // wave 0: the tile totals, and their sum for the scan's group totals
+    uint64_t tot = 0;
+    if (tid < V1CT && t0 + tid < ntiles) {
+#pragma unroll
+      for (uint32_t w = 0; w < V1T / 64; w++) tot += red[tid][w];
+      sums[t0 + tid] = tot;
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)tot, o, 64), hi = __shfl_xor((uint32_t)(tot >> 32), o, 64);
+      tot += (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    if (tid == 0) gsums[blockIdx.x] = tot;
+  }
+}
+
+template <int DT_X>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_resid_fitted(FieldDesc F, uint32_t maxprec,
+                                                                        const int32_t* __restrict__ d_minexp,
+                                                                        const float* e_in, float* e_out,
+                                                                        const uint64_t* __restrict__ rbase,
+                                                                        const uint32_t* __restrict__ lens8,
+                                                                        uint32_t* __restrict__ out32,
+                                                                        uint64_t* __restrict__ index,
+                                                                        uint32_t index_shift, uint32_t ntiles,
+                                                                        uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t t = blockIdx.x;
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  // as in k_encode1d_var_tile_resid, every load the tile needs is issued before anything else waits
+  V1Raw<DT_F32> y;
+  v1_load_y<DT_X>(F, e_in, t, y);
+  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  const uint64_t B = rbase[t];
+  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel, nothing stored here
+    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
+    return;
+  }
+  v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
+}
+
+template <int DT_X>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid_fitted(FieldDesc F, uint32_t maxprec,
+                                                                            const int32_t* __restrict__ d_minexp,
+                                                                            const float* e_in, float* e_out,
+                                                                            const uint64_t* __restrict__ rbase,
+                                                                            const uint32_t* __restrict__ lens8,
+                                                                            uint32_t* __restrict__ out32,
+                                                                            uint64_t* __restrict__ index,
+                                                                            uint32_t index_shift, uint32_t ntiles,
+                                                                            const uint32_t* __restrict__ over)
+{
+  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
+  __shared__ uint32_t rs[1024];
+  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
+  __shared__ uint32_t scan_sh[V1T / 64];
+  __shared__ uint32_t s_special;
+  const uint32_t n = over[0];
+  if (blockIdx.x >= n) return;
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
+#pragma unroll
+  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t t = over[1 + i];
+    const uint64_t B = rbase[t];
+    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+    V1Raw<DT_F32> y;
+    v1_load_y<DT_X>(F, e_in, t, y);
+    const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+    v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh,
+                  &s_special);
+    __syncthreads();  // the window and scan slots are reused by the next tile
+  }
+}
+
+template <int DT_X>
+static hipError_t launch_resid1d_var_fitted_t(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
+                                              const float* e_in, float* e_out, uint32_t* out32, uint64_t* ws,
+                                              uint64_t* d_total, uint64_t* index, uint32_t index_shift, hipStream_t st)
+{
+  // the tile form's workspace layout (launch_encode1d_var_tile)
+  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
+  uint64_t* sums = ws;
+  uint64_t* base = ws + ntiles;
+  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
+  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
+  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
+  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
+  if (e_in)
+    k_count1d_var_tile_resid_fitted<DT_X, true><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, ntiles, sums, lens8,
+                                                                     over, gsums);
+  else
+    k_count1d_var_tile_resid_fitted<DT_X, false><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, nullptr, ntiles, sums,
+                                                                      lens8, over, gsums);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
+  if (e != hipSuccess) return e;
+  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
+  k_encode1d_var_tile_resid_fitted<DT_X><<<ntiles, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, e_out, base, lens8, out32,
+                                                                 index, index_shift, ntiles, over);
+  k_encode1d_var_tile_big_resid_fitted<DT_X><<<nbig, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, e_out, base, lens8,
+                                                                   out32, index, index_shift, ntiles, over);
+  return hipGetLastError();
+}
+
+hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t nvals, uint32_t maxprec,
+                                            const int32_t* d_minexp, const float* e_in, float* e_out, uint32_t* out32,
+                                            uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
+                                            void* stream)
+{
+  FieldDesc F = {};  // launch_encode_resid1d_var's descriptor
+  F.data = x;
+  F.n[0] = nvals;
+  F.n[1] = F.n[2] = F.n[3] = 1;
+  F.s[0] = 1;
+  F.nblocks = F.bx = (uint32_t)((nvals + 3) / 4);
+  F.by = F.bz = F.bw = 1;
+  F.dims = 1;
+  F.dtype = (uint32_t)x_dtype;
+  F.vec = ((uintptr_t)x % (x_dtype == DT_BF16 ? 8u : 16u)) == 0 ? 1u : 0u;
+  if (x_dtype == DT_BF16)
+    return launch_resid1d_var_fitted_t<DT_BF16>(F, maxprec, d_minexp, e_in, e_out, out32, ws, d_total, index,
+                                                index_shift, (hipStream_t)stream);
+  return launch_resid1d_var_fitted_t<DT_F32>(F, maxprec, d_minexp, e_in, e_out, out32, ws, d_total, index, index_shift,
+                                             (hipStream_t)stream);
+}
+
 }  // namespace gcow

@@ -26,7 +26,9 @@ Accuracy mode under a bit budget (`GcowHookState.target_bits`, all three hooks):
 in bits per value from the bucket's rate table (codec.rate_table: the stream length under every minexp from one pass);
 roundtrip_hook bounds the budget, the wire hooks track it with a control lagged by one step -- or, with
 `GcowHookState.fit_on_device`, compressed_allgather_hook fits the very step it encodes: table, fit and encode run on
-the device back to back (codec.fit_device, codec.encode_fitted_device), and the step's streams meet the budget.
+the device back to back (codec.fit_device, codec.encode_fitted_device), and the step's streams meet the budget -- with
+error feedback too: the table is then of bucket + carried error (codec.rate_table_residual) and the encode is
+codec.encode_residual_fitted_device, so the bound holds for what is sent.
 """
 import contextlib
 import queue
@@ -124,10 +126,16 @@ class GcowHookState:
     world * floor(target_bits * n) bits -- the budget is bounded, not tracked, and step 1 is fitted like every other.
     A budget below one bit per block cannot be met: the record's status is 1 and the coarsest set (minexp 133) is
     used, as the lagged control does. The price is latency: table, all-reduce (2.3 KB) and fit now run before the
-    encode instead of beside it, and the encode no longer overlaps the autograd thread's work. Combined with
-    `error_feedback` or `compress_mean`, or registered with compressed_sharded_hook: ValueError -- those encodes are
-    other kernel families. A codec without rate_table, fit_device, encode_fitted and
-    roundtrip_fitted: ValueError. Unset (the default): nothing changes."""
+    encode instead of beside it, and the encode no longer overlaps the autograd thread's work.
+    compressed_allgather_hook with `error_feedback` as well: the table is taken of y = bucket + carried error
+    (codec.rate_table_residual, y formed in registers), summed and fitted as above, and y is encoded under the record
+    by codec.encode_residual_fitted_device, which updates the carried error in place; the error buffer is obtained on
+    the autograd thread, everything else runs inside the exchange. The W streams of this step total at most
+    world * floor(target_bits * n) bits, and that holds for what is actually sent, y -- where the lagged control fits
+    the bucket alone. The codec must also have rate_table_residual and encode_residual_fitted, else ValueError.
+    Combined with `compress_mean`, registered with compressed_sharded_hook, or roundtrip_hook with `error_feedback`:
+    ValueError -- those encodes are other kernel families. A codec without rate_table,
+    fit_device, encode_fitted and roundtrip_fitted: ValueError. Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -261,18 +269,24 @@ class GcowHookState:
         if not self.fit_on_device:
             return False
         why = None
-        if self.error_feedback:
+        resid = self.error_feedback and hook_name == "compressed_allgather_hook" and not self.compress_mean
+        if self.error_feedback and not resid:
             why = "error_feedback encodes with the residual form, another kernel family"
         elif self.compress_mean:
             why = "compress_mean encodes the mean with the reduce encoder, another kernel family"
         elif hook_name == "compressed_sharded_hook":
             why = "compressed_sharded_hook decodes the pieces it receives under host parameters in the same exchange"
         if why:
-            raise ValueError("fit_on_device is for roundtrip_hook and compressed_allgather_hook without error "
-                             "feedback: " + why)
+            raise ValueError("fit_on_device is for roundtrip_hook, and for compressed_allgather_hook with or without "
+                             "error feedback: " + why)
         missing = [m for m in ("rate_table", "fit_device", "encode_fitted", "roundtrip_fitted") if not hasattr(cdc, m)]
         if missing:
             raise ValueError("fit_on_device needs a codec with %s (gcow_amd.dist.DeviceCodec)" % ", ".join(missing))
+        if resid:  # the table of bucket + carried error, and the residual encode under the device record
+            missing = [m for m in ("rate_table_residual", "encode_residual_fitted") if not hasattr(cdc, m)]
+            if missing:
+                raise ValueError("fit_on_device with error_feedback needs a codec with %s "
+                                 "(gcow_amd.dist.DeviceCodec)" % ", ".join(missing))
         return True
 
     def side_stream(self, dev):
@@ -473,6 +487,10 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     state.check_target()
     cdc = state.get_codec()
     fod = state.check_fit_on_device(cdc, "compressed_allgather_hook")  # before any collective
+    if fod and not (dist.is_available() and dist.is_initialized()):
+        # said here, with the state's modes, and not by torch's "default process group" error from the line below
+        raise ValueError("compressed_allgather_hook with fit_on_device (error_feedback=%s) encodes inside the "
+                         "exchange and needs an initialised process group" % state.error_feedback)
     group = state.process_group
     buf = bucket.buffer()
     world = dist.get_world_size(group)
@@ -497,8 +515,11 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
 
         return fut.then(finish)
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
+    err = None
     if fod:  # encoded inside the exchange, under this step's own fit
         words = bits = index = table = None
+        if state.error_feedback:  # obtained here (zeros at first use, on this stream); it lives on the state
+            err = state.error_buffer(slot, x)
     else:
         words, bits, index8 = _encode(state, cdc, bucket, x, SHARDED_INDEX_STRIDE, slot, p)
         index = cdc.pack_index16(index8, n, p)  # what travels: one entry per 16 blocks
@@ -526,12 +547,19 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
                         t.record_stream(side)
             rec = None
             if fod:  # this step's table, summed over the ranks, fitted and encoded under on the device
-                tab = _rate_table(state, cdc, x, slot)
+                if err is not None:  # of y = x + e, what is encoded and sent
+                    tab = cdc.rate_table_residual(x, err, p.maxprec, slot=("rate", slot))
+                else:
+                    tab = _rate_table(state, cdc, x, slot)
                 if world > 1:
                     dist.all_reduce(tab, group=cgroup)
                 rec = cdc.fit_device(tab, world * _budget(state, n), slot=("fit", slot))
                 state._fit_records[slot] = rec
-                words, bits, index8 = cdc.encode_fitted(x, rec, p.maxprec, SHARDED_INDEX_STRIDE, slot=slot)
+                if err is not None:  # e is updated in place: y - decode(stream) under the fitted set
+                    words, bits, index8 = cdc.encode_residual_fitted(x, err, rec, p.maxprec, SHARDED_INDEX_STRIDE,
+                                                                     slot=slot)
+                else:
+                    words, bits, index8 = cdc.encode_fitted(x, rec, p.maxprec, SHARDED_INDEX_STRIDE, slot=slot)
                 index = cdc.pack_index16(index8, n, p)  # the packing reads no minexp
             elif table is not None:
                 _fit_next(state, table, slot, n, world, cgroup)

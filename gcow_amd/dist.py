@@ -152,6 +152,16 @@ class DeviceCodec:
         self._evict_idle()
         return ent[0](x if x.is_contiguous() else x.contiguous(), maxprec)
 
+    def rate_table_residual(self, x: torch.Tensor, err: torch.Tensor, maxprec: int = 64, slot=None) -> torch.Tensor:
+        """The rate table of y = x + err, the array `encode_residual` codes (codec.rate_table_residual): entry t the
+        bits `encode_residual(x, err, expert(1, 16658, maxprec, -154 + t))` reports. x and err are only read. Cached
+        as `rate_table`'s, apart from them."""
+        from . import codec
+        x = x.reshape(-1)
+        key = (slot, x.numel(), x.dtype, x.device, "rate_table_residual")
+        rt = self._cached(key, lambda: codec.RateTable(x.numel(), x.dtype, x.device))
+        return rt(x if x.is_contiguous() else x.contiguous(), maxprec, err=err)
+
     def _cached(self, key, make):
         self._tick += 1
         ent = self._enc.get(key)
@@ -182,6 +192,19 @@ class DeviceCodec:
         enc = self._cached(key, lambda: codec.Encoder((x.numel(),), x.dtype, codec.fitted_params(maxprec, 0),
                                                       x.device, index_stride))
         e = codec._encode_fitted_into(enc, x if x.is_contiguous() else x.contiguous(), minexp_word)
+        return e.words, e.bits_dev, e.index
+
+    def encode_residual_fitted(self, x: torch.Tensor, err: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64,
+                               index_stride: int = 0, slot=None):
+        """`encode_residual` under the set minexp_word stands for, read on the device
+        (codec.encode_residual_fitted_device): -> (words, bits, index), `err` updated in place. Output buffers cached
+        per slot like `encode_fitted`'s, apart from theirs."""
+        from . import codec
+        x = x.reshape(-1)
+        key = (slot, x.numel(), x.dtype, x.device, int(maxprec), index_stride, "fitted", "residual")
+        enc = self._cached(key, lambda: codec.Encoder((x.numel(),), torch.float32, codec.fitted_params(maxprec, 0),
+                                                      x.device, index_stride))
+        e = codec._encode_residual_fitted_into(enc, x if x.is_contiguous() else x.contiguous(), err, minexp_word)
         return e.words, e.bits_dev, e.index
 
     def roundtrip_fitted(self, x: torch.Tensor, minexp_word: torch.Tensor, maxprec: int = 64, out=None):

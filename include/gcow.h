@@ -467,12 +467,24 @@ gcow_status gcow_roundtrip_rel_device(const void* h_plan, const void* d_plan, si
  * gcow_rate_table_fit (HOST; h_table: a host copy of the 288 entries): the smallest minexp in [-154, 133] whose entry
  * is <= budget_bits -- the finest tolerance whose stream fits -- and that entry. GCOW_ERR_INVALID when budget_bits <
  * h_table[287]: no accuracy-mode stream is shorter than one bit per block (*minexp and *bits are left alone).
+ *
+ * gcow_rate_table_residual_device: the table of y, y[i] = (float)x[i] + e_in[i] -- the array error feedback encodes.
+ * The add is the single __fadd_rn of gcow_encode_residual_device step 1 (a bf16 x widened exactly); the pass forms y in
+ * registers and never writes it to memory. d_table[t] is exactly the *d_total_bits gcow_encode_residual_device reports
+ * for the same field and d_err_in under {1, 16658, maxprec, -154 + t}. d_err_in (DEVICE, n floats): any 4-byte aligned
+ * address; NULL means zeros, and the table is gcow_rate_table_device's. Wide loads run when field->data and d_err_in
+ * are both 16-byte aligned, else the element path; the partial last block is padded from y, as the encoder pads it.
+ * Workspace, table, stream behaviour and errors as gcow_rate_table_device (the workspace query is unchanged), plus
+ * GCOW_ERR_INVALID for a d_err_in off 4 bytes.
  */
 #define GCOW_RATE_TABLE_MINEXP_LO (-154)
 #define GCOW_RATE_TABLE_ENTRIES 288
 size_t gcow_rate_table_workspace_bytes(const zfp_input* field);
 gcow_status gcow_rate_table_device(const zfp_input* field, uint32_t maxprec, uint64_t* d_table, void* d_workspace,
                                    size_t workspace_bytes, void* hip_stream);
+gcow_status gcow_rate_table_residual_device(const zfp_input* field, const float* d_err_in, uint32_t maxprec,
+                                            uint64_t* d_table, void* d_workspace, size_t workspace_bytes,
+                                            void* hip_stream);
 gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, int* minexp, uint64_t* bits);
 
 /*
@@ -508,6 +520,18 @@ gcow_status gcow_rate_table_fit(const uint64_t* h_table, uint64_t budget_bits, i
  * when the dtypes are equal. Buffers off 16-byte alignment and the partial last block go through the generic kernel
  * under the same device word. Errors as gcow_roundtrip_device's, and GCOW_ERR_INVALID for a NULL or misaligned d_minexp.
  *
+ * gcow_encode_residual_fitted_device: error feedback under the device word. With m as above, every output is byte for
+ * byte what gcow_encode_residual_device(field, {1, 16658, maxprec, m}, d_err_in, d_err_out, ...) writes on its
+ * GCOW_RESID_FUSED_VAR path: the stream, *d_total_bits, the index, the zeroed flush word and e_out; nothing is written
+ * past e_out[n - 1]. d_err_in == d_err_out is allowed, d_err_in == NULL means zeros. Always the tile form with the
+ * residual; there is no composed fallback, because its decoder takes host parameters: field->data, d_err_in or
+ * d_err_out off 16-byte alignment returns GCOW_ERR_UNSUPPORTED and writes nothing. The workspace is
+ * gcow_encode_workspace_bytes and out_capacity gcow_max_output_bytes of the fp32 field of n values under
+ * {1, 16658, maxprec, any minexp}: NEITHER DEPENDS ON minexp, so both can be sized before the fit exists. With
+ * gcow_rate_table_residual_device and gcow_rate_table_fit_device ahead of it on the stream, table of y, fit and encode
+ * run with no host read and the stream is within the budget for y, the array that is sent. nx = 0 writes
+ * *d_total_bits = 0. Other errors as gcow_encode_fitted_device's, and GCOW_ERR_INVALID for a NULL d_err_out.
+ *
  * Decoders are untouched: a stream is decoded under host parameters. A caller that needs minexp on the host reads the
  * 16-byte record when it next has to wait anyway.
  */
@@ -521,6 +545,11 @@ gcow_status gcow_encode_fitted_device(const zfp_input* field, uint32_t maxprec, 
                                       size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
                                       size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
                                       void* hip_stream);
+gcow_status gcow_encode_residual_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp,
+                                               const float* d_err_in, float* d_err_out, void* d_out,
+                                               size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                               size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                               void* hip_stream);
 gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxprec, const int32_t* d_minexp, void* d_out,
                                          data_type out_dtype, uint64_t* d_total_bits, void* hip_stream);
 
