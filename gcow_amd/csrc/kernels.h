@@ -207,6 +207,9 @@ static_assert(sizeof(RateFit) == 16 && alignof(RateFit) == 8, "gcow_fit");
 hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, RateFit* fit, void* stream);
 // Device-parameter ("fitted") forms: Params{1, 16658, maxprec, clamp(*d_minexp, -154, 133)} with the word read on the
 // device when the kernels run (fitted_params_dev, var1d_prep.h). Nothing on the host depends on minexp.
+// The tile-form kernels of var1d.hip are templates over their parameter source (ParamsHost / ParamsDev, var1d_prep.h):
+// the two launchers below run the kernels of launch_encode1d_var_tile / launch_encode_resid1d_var with ParamsDev. The
+// round trip (roundtrip1d.hip) keeps kernels of its own for the device word.
 // The tile form of the 1-D variable-rate encoder (var1d.hip), ws = var1d_tile_workspace_bytes(): every output as
 // launch_encode1d_var_tile writes it under that set (no d_base). Always the tile form: g_var1d_variant does not apply.
 hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,

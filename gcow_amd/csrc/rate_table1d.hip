@@ -315,43 +315,33 @@ hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, Ra
 
 size_t rate_table_workspace_bytes() { return 2 * RT_BINS * sizeof(uint64_t); }
 
-hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream)
-{
-  hipStream_t st = (hipStream_t)stream;
-  k_rate_table_zero<<<1, RT_BINS, 0, st>>>((unsigned long long*)ws);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const uint32_t pmax = std::min(maxprec, 32u);
-  if (F.nblocks && pmax) {
-    const uint32_t ntiles = (uint32_t)(((uint64_t)F.nblocks + RT_TILE - 1) / RT_TILE);
-    const uint32_t grid = std::min(ntiles, RT_MAXGRID);
-    if (F.dtype == DT_BF16) k_rate_table1d<DT_BF16><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
-    else k_rate_table1d<DT_F32><<<grid, RTT, 0, st>>>(F, pmax, ntiles, (unsigned long long*)ws);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  k_rate_table_finish<<<1, RT_BINS, 0, st>>>((const unsigned long long*)ws, F.nblocks, table);
-  return hipGetLastError();
-}
-
+// zero -> pass -> finish; e_in null: the table of x (y = x + 0 codes as x), else of y = x + e
 hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint32_t maxprec, uint64_t* table,
                                      uint64_t* ws, void* stream)
 {
-  if (!e_in) return launch_rate_table1d(F, maxprec, table, ws, stream);  // y = x + 0 codes as x
   hipStream_t st = (hipStream_t)stream;
-  k_rate_table_zero<<<1, RT_BINS, 0, st>>>((unsigned long long*)ws);
+  unsigned long long* w = (unsigned long long*)ws;
+  k_rate_table_zero<<<1, RT_BINS, 0, st>>>(w);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint32_t pmax = std::min(maxprec, 32u);
   if (F.nblocks && pmax) {
     const uint32_t ntiles = (uint32_t)(((uint64_t)F.nblocks + RT_TILE - 1) / RT_TILE);
     const uint32_t grid = std::min(ntiles, RT_MAXGRID);
-    if (F.dtype == DT_BF16)
-      k_rate_table1d_xe<DT_BF16><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, (unsigned long long*)ws);
-    else k_rate_table1d_xe<DT_F32><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, (unsigned long long*)ws);
+    const bool bf16 = F.dtype == DT_BF16;
+    if (!e_in && bf16) k_rate_table1d<DT_BF16><<<grid, RTT, 0, st>>>(F, pmax, ntiles, w);
+    else if (!e_in) k_rate_table1d<DT_F32><<<grid, RTT, 0, st>>>(F, pmax, ntiles, w);
+    else if (bf16) k_rate_table1d_xe<DT_BF16><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, w);
+    else k_rate_table1d_xe<DT_F32><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  k_rate_table_finish<<<1, RT_BINS, 0, st>>>((const unsigned long long*)ws, F.nblocks, table);
+  k_rate_table_finish<<<1, RT_BINS, 0, st>>>(w, F.nblocks, table);
   return hipGetLastError();
+}
+
+hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream)
+{
+  return launch_rate_table1d_resid(F, nullptr, maxprec, table, ws, stream);
 }
 
 }  // namespace gcow

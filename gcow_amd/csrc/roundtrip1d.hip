@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <stdint.h>
+#include <type_traits>
 #include <utility>
 
 #include "field_io.h"
@@ -113,64 +114,6 @@ __global__ __launch_bounds__(256) void k_roundtrip1d_generic(const void* in, uin
   if (total) rt_count(len, cnt_sh, total);  // total: a kernel argument, uniform over the workgroup
 }
 
-// ------------------------------------------------------------------------------------------------ launchers
-template <int DT_IN, int DT_OUT>
-static void launch_rt_generic(const void* in, uint64_t nvals, uint64_t b0, uint64_t nb, const Params& p, void* out,
-                              uint64_t* total, hipStream_t st)
-{
-  constexpr uint64_t CH = 1ull << 30;  // blocks per launch: the grid stays below 2^31 workgroups
-  for (uint64_t c0 = 0; c0 < nb; c0 += CH) {
-    const uint64_t nc = std::min(CH, nb - c0);
-    k_roundtrip1d_generic<DT_IN, DT_OUT><<<(uint32_t)((nc + 255) / 256), 256, 0, st>>>(in, nvals, b0 + c0, nc, p, out,
-                                                                                      total);
-  }
-}
-
-template <int DT_IN, int DT_OUT>
-static void launch_rt_t(const void* in, uint64_t nvals, const Params& p, int domain, void* out, uint64_t* total,
-                        hipStream_t st)
-{
-  const uint64_t nblocks = (nvals + 3) / 4;
-  if (domain == kRoundtripGeneric) {
-    launch_rt_generic<DT_IN, DT_OUT>(in, nvals, 0, nblocks, p, out, total, st);
-    return;
-  }
-  const uint32_t nfull = (uint32_t)(nvals / 4);
-  // chunks keep every offset into the two buffers below 2^32 (16 bytes per block at most)
-  constexpr uint32_t CH = 1u << 27;
-  constexpr uint32_t IB = rt_row_bytes<DT_IN>(), OB = rt_row_bytes<DT_OUT>();
-  constexpr int U = GCOW_RT_U;
-  for (uint32_t c0 = 0; c0 < nfull; c0 += CH) {
-    const uint32_t nc = std::min(CH, nfull - c0);
-    const void* ic = (const char*)in + (size_t)c0 * IB;
-    void* oc = (char*)out + (size_t)c0 * OB;
-    const uint32_t g = (nc + 256 * U - 1) / (256 * U);
-    if (domain == kRoundtripLean) {
-      if (p.maxbits == 64) k_roundtrip1d_fixed_np<DT_IN, DT_OUT, 64, U><<<g, 256, 0, st>>>(ic, nc, p, oc);
-      else k_roundtrip1d_fixed_np<DT_IN, DT_OUT, 32, U><<<g, 256, 0, st>>>(ic, nc, p, oc);
-    } else if (total) {
-      k_roundtrip1d_var<DT_IN, DT_OUT, true><<<g, 256, 0, st>>>(ic, nc, p, oc, total);
-    } else {
-      k_roundtrip1d_var<DT_IN, DT_OUT, false><<<g, 256, 0, st>>>(ic, nc, p, oc, nullptr);
-    }
-  }
-  if (nvals % 4) launch_rt_generic<DT_IN, DT_OUT>(in, nvals, nfull, 1, p, out, total, st);
-}
-
-hipError_t launch_roundtrip1d(const void* in, int in_dtype, uint64_t nvals, const Params& p, int domain, void* out,
-                              int out_dtype, uint64_t* total, void* stream)
-{
-  hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == DT_F32) {
-    if (out_dtype == DT_F32) launch_rt_t<DT_F32, DT_F32>(in, nvals, p, domain, out, total, st);
-    else launch_rt_t<DT_F32, DT_BF16>(in, nvals, p, domain, out, total, st);
-  } else {
-    if (out_dtype == DT_F32) launch_rt_t<DT_BF16, DT_F32>(in, nvals, p, domain, out, total, st);
-    else launch_rt_t<DT_BF16, DT_BF16>(in, nvals, p, domain, out, total, st);
-  }
-  return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------ minexp from the device
 // gcow_roundtrip_fitted_device (include/gcow.h): kernels (b) and (c) under
 // Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernel runs (fitted_params_dev, var1d_prep.h).
@@ -220,29 +163,48 @@ __global__ __launch_bounds__(256) void k_roundtrip1d_generic_fitted(const void* 
   if (total) rt_count(len, cnt_sh, total);  // total: a kernel argument, uniform over the workgroup
 }
 
-template <int DT_IN, int DT_OUT>
-static void launch_rt_generic_fitted(const void* in, uint64_t nvals, uint64_t b0, uint64_t nb, uint32_t maxprec,
-                                     const int32_t* d_minexp, void* out, uint64_t* total, hipStream_t st)
+// ------------------------------------------------------------------------------------------------ launchers
+// One set for both parameter sources (ParamsHost / ParamsDev, var1d_prep.h): the source picks a kernel or its _fitted
+// twin, which keep their own argument lists (as templates over the source their device code changed).
+template <int DT_IN, int DT_OUT, class PS>
+static void launch_rt_generic(const void* in, uint64_t nvals, uint64_t b0, uint64_t nb, const PS& ps, void* out,
+                              uint64_t* total, hipStream_t st)
 {
   constexpr uint64_t CH = 1ull << 30;  // blocks per launch: the grid stays below 2^31 workgroups
   for (uint64_t c0 = 0; c0 < nb; c0 += CH) {
     const uint64_t nc = std::min(CH, nb - c0);
-    k_roundtrip1d_generic_fitted<DT_IN, DT_OUT><<<(uint32_t)((nc + 255) / 256), 256, 0, st>>>(
-        in, nvals, b0 + c0, nc, maxprec, d_minexp, out, total);
+    const uint32_t g = (uint32_t)((nc + 255) / 256);
+    if constexpr (std::is_same<PS, ParamsHost>::value)
+      k_roundtrip1d_generic<DT_IN, DT_OUT><<<g, 256, 0, st>>>(in, nvals, b0 + c0, nc, ps.p, out, total);
+    else
+      k_roundtrip1d_generic_fitted<DT_IN, DT_OUT><<<g, 256, 0, st>>>(in, nvals, b0 + c0, nc, ps.maxprec, ps.d_minexp,
+                                                                     out, total);
   }
 }
 
-template <int DT_IN, int DT_OUT>
-static void launch_rt_fitted_t(const void* in, uint64_t nvals, uint32_t maxprec, const int32_t* d_minexp, bool rows16,
-                               void* out, uint64_t* total, hipStream_t st)
+template <int DT_IN, int DT_OUT, bool COUNT, class PS>
+static void launch_rt_var(const void* in, uint32_t nfull, const PS& ps, void* out, uint64_t* total, uint32_t g,
+                          hipStream_t st)
+{
+  if constexpr (std::is_same<PS, ParamsHost>::value)
+    k_roundtrip1d_var<DT_IN, DT_OUT, COUNT><<<g, 256, 0, st>>>(in, nfull, ps.p, out, total);
+  else
+    k_roundtrip1d_var_fitted<DT_IN, DT_OUT, COUNT><<<g, 256, 0, st>>>(in, nfull, ps.maxprec, ps.d_minexp, out, total);
+}
+
+// domain: ParamsHost any; ParamsDev kRoundtripVar or kRoundtripGeneric (the lean kernel is host-parameter only)
+template <int DT_IN, int DT_OUT, class PS>
+static void launch_rt_t(const void* in, uint64_t nvals, const PS& ps, int domain, void* out, uint64_t* total,
+                        hipStream_t st)
 {
   const uint64_t nblocks = (nvals + 3) / 4;
-  if (!rows16) {
-    launch_rt_generic_fitted<DT_IN, DT_OUT>(in, nvals, 0, nblocks, maxprec, d_minexp, out, total, st);
+  if (domain == kRoundtripGeneric) {
+    launch_rt_generic<DT_IN, DT_OUT>(in, nvals, 0, nblocks, ps, out, total, st);
     return;
   }
   const uint32_t nfull = (uint32_t)(nvals / 4);
-  constexpr uint32_t CH = 1u << 27;  // launch_rt_t's chunks: every buffer offset stays below 2^32
+  // chunks keep every offset into the two buffers below 2^32 (16 bytes per block at most)
+  constexpr uint32_t CH = 1u << 27;
   constexpr uint32_t IB = rt_row_bytes<DT_IN>(), OB = rt_row_bytes<DT_OUT>();
   constexpr int U = GCOW_RT_U;
   for (uint32_t c0 = 0; c0 < nfull; c0 += CH) {
@@ -250,25 +212,47 @@ static void launch_rt_fitted_t(const void* in, uint64_t nvals, uint32_t maxprec,
     const void* ic = (const char*)in + (size_t)c0 * IB;
     void* oc = (char*)out + (size_t)c0 * OB;
     const uint32_t g = (nc + 256 * U - 1) / (256 * U);
-    if (total) k_roundtrip1d_var_fitted<DT_IN, DT_OUT, true><<<g, 256, 0, st>>>(ic, nc, maxprec, d_minexp, oc, total);
-    else k_roundtrip1d_var_fitted<DT_IN, DT_OUT, false><<<g, 256, 0, st>>>(ic, nc, maxprec, d_minexp, oc, nullptr);
+    if (domain == kRoundtripLean) {
+      if constexpr (std::is_same<PS, ParamsHost>::value) {
+        if (ps.p.maxbits == 64) k_roundtrip1d_fixed_np<DT_IN, DT_OUT, 64, U><<<g, 256, 0, st>>>(ic, nc, ps.p, oc);
+        else k_roundtrip1d_fixed_np<DT_IN, DT_OUT, 32, U><<<g, 256, 0, st>>>(ic, nc, ps.p, oc);
+      }
+    } else if (total) {
+      launch_rt_var<DT_IN, DT_OUT, true>(ic, nc, ps, oc, total, g, st);
+    } else {
+      launch_rt_var<DT_IN, DT_OUT, false>(ic, nc, ps, oc, nullptr, g, st);
+    }
   }
-  if (nvals % 4) launch_rt_generic_fitted<DT_IN, DT_OUT>(in, nvals, nfull, 1, maxprec, d_minexp, out, total, st);
+  if (nvals % 4) launch_rt_generic<DT_IN, DT_OUT>(in, nvals, nfull, 1, ps, out, total, st);
+}
+
+template <class PS>
+static hipError_t launch_rt(const void* in, int in_dtype, uint64_t nvals, const PS& ps, int domain, void* out,
+                            int out_dtype, uint64_t* total, void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  if (in_dtype == DT_F32) {
+    if (out_dtype == DT_F32) launch_rt_t<DT_F32, DT_F32>(in, nvals, ps, domain, out, total, st);
+    else launch_rt_t<DT_F32, DT_BF16>(in, nvals, ps, domain, out, total, st);
+  } else {
+    if (out_dtype == DT_F32) launch_rt_t<DT_BF16, DT_F32>(in, nvals, ps, domain, out, total, st);
+    else launch_rt_t<DT_BF16, DT_BF16>(in, nvals, ps, domain, out, total, st);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_roundtrip1d(const void* in, int in_dtype, uint64_t nvals, const Params& p, int domain, void* out,
+                              int out_dtype, uint64_t* total, void* stream)
+{
+  return launch_rt(in, in_dtype, nvals, ParamsHost{p}, domain, out, out_dtype, total, stream);
 }
 
 hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nvals, uint32_t maxprec,
                                      const int32_t* d_minexp, bool rows16, void* out, int out_dtype, uint64_t* total,
                                      void* stream)
 {
-  hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == DT_F32) {
-    if (out_dtype == DT_F32) launch_rt_fitted_t<DT_F32, DT_F32>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
-    else launch_rt_fitted_t<DT_F32, DT_BF16>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
-  } else {
-    if (out_dtype == DT_F32) launch_rt_fitted_t<DT_BF16, DT_F32>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
-    else launch_rt_fitted_t<DT_BF16, DT_BF16>(in, nvals, maxprec, d_minexp, rows16, out, total, st);
-  }
-  return hipGetLastError();
+  return launch_rt(in, in_dtype, nvals, ParamsDev{maxprec, d_minexp}, rows16 ? kRoundtripVar : kRoundtripGeneric, out,
+                   out_dtype, total, stream);
 }
 
 }  // namespace gcow

@@ -506,7 +506,10 @@ hipError_t launch_encode1d_var_sp(const FieldDesc& F, const Params& p, uint32_t*
 //                        not VALU issue, bounds it); a tile that needs more is skipped and coded by
 //   k_encode1d_var_tile_big  the same body with the worst-case window (140 bits per block), a grid-stride loop over
 //                        the list of oversized tiles k_encode1d_var_tile appended to (the count kernel empties it).
-constexpr uint32_t V1CT = 8;                                      // tiles per count workgroup
+// The kernels exist for the field's own values and, named _resid, for y = x + e with the residual e' written by the
+// coders; each is a template over its parameter source (ParamsHost / ParamsDev, var1d_prep.h). The device functions
+// come first; the kernels, the one launcher and the workspace layout are at the end of this file.
+constexpr uint32_t V1CT = 8;                                     // tiles per count workgroup
 constexpr uint32_t V1QS = 1500 * (V1T / 256);                     // small window, qwords (95 bits per block)
 constexpr uint32_t V1TAB = 1024;                                  // pair-table rows 0..3 in LDS
 
@@ -586,84 +589,6 @@ __device__ __forceinline__ uint32_t v1_count_tile(const FieldDesc& F, const Para
     lsum += len;
   }
   return pk;
-}
-
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_count1d_var_tile(FieldDesc F, Params p, uint32_t ntiles,
-                                                          uint64_t* __restrict__ sums, uint32_t* __restrict__ lens8,
-                                                          uint32_t* __restrict__ nover, uint64_t* __restrict__ gsums)
-{
-  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
-  // V1CT consecutive tiles per workgroup. Full contiguous tiles are software-pipelined: tile i + 1's raw buffer loads
-  // are issued before tile i is counted (hand-counted waits), and nothing is stored until the loop is done -- the
-  // workgroups of a one-shot grid otherwise run in lock step, all loading and then all computing.
-  __shared__ uint32_t red[V1CT][V1T / 64];
-  const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
-  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile starts empty
-  const bool wide_ok = F.vec && (((uintptr_t)F.data) & 15u) == 0;
-  constexpr int NL = V1Raw<DT>::N;                                 // 16-byte loads per lane per tile
-  constexpr uint32_t TB = V1TILE * (DT == DT_BF16 ? 8u : 16u);     // bytes per tile
-  uint32_t packed[V1CT];
-  if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
-    const v1_v4i rs = v1_rsrc((const char*)F.data + (size_t)t0 * TB, V1CT * TB);
-    // a ring of PF + 1 tiles: tile i + PF is requested before tile i is counted, so PF tiles of loads stay in flight
-    constexpr uint32_t PF = V1_COUNT_PF, RING = PF + 1;
-    v1_u4 buf[RING][NL];
-#pragma unroll
-    for (uint32_t i = 0; i < PF && i < V1CT; i++)
-#pragma unroll
-      for (int h = 0; h < NL; h++) buf[i][h] = v1_ld16(i * TB + (tid * NL + h) * 16u, rs);
-#pragma unroll
-    for (uint32_t i = 0; i < V1CT; i++) {
-      if (i + PF < V1CT) {
-#pragma unroll
-        for (int h = 0; h < NL; h++) buf[(i + PF) % RING][h] = v1_ld16((i + PF) * TB + (tid * NL + h) * 16u, rs);
-      }
-      // loads issued after tile i's: those of tiles i + 1 .. min(i + PF, V1CT - 1)
-      v1_wait_tiles<NL>(buf[i % RING], (i + PF < V1CT ? PF : V1CT - 1 - i));
-      V1Raw<DT> cur;
-#pragma unroll
-      for (int h = 0; h < NL; h++) {
-        const v1_u4 v = buf[i % RING][h];
-        cur.w[h] = make_uint4(v.x, v.y, v.z, v.w);
-      }
-      uint32_t lsum;
-      packed[i] = v1_count_tile<DT, true>(F, p, cur, t0 + i, lsum);
-      lsum = wave_sum_dpp(lsum);
-      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
-    }
-  } else {  // partial tiles, the padded last block, strided or unaligned input
-#pragma unroll
-    for (uint32_t i = 0; i < V1CT; i++) {
-      uint32_t lsum = 0;
-      packed[i] = 0;
-      if (t0 + i < ntiles) {
-        V1Raw<DT> raw;
-        raw.load(F, t0 + i, wide_ok);
-        packed[i] = v1_count_tile<DT>(F, p, raw, t0 + i, lsum);
-      }
-      lsum = wave_sum_dpp(lsum);
-      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
-    }
-  }
-#pragma unroll
-  for (uint32_t i = 0; i < V1CT; i++)
-    if (t0 + i < ntiles) lens8[(size_t)(t0 + i) * V1T + tid] = packed[i];
-  __syncthreads();
-  if (tid < 64) {  // wave 0: the tile totals, and their sum for the scan's group totals
-    uint64_t tot = 0;
-    if (tid < V1CT && t0 + tid < ntiles) {
-#pragma unroll
-      for (uint32_t w = 0; w < V1T / 64; w++) tot += red[tid][w];
-      sums[t0 + tid] = tot;
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-      const uint32_t lo = __shfl_xor((uint32_t)tot, o, 64), hi = __shfl_xor((uint32_t)(tot >> 32), o, 64);
-      tot += (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    if (tid == 0) gsums[blockIdx.x] = tot;
-  }
 }
 
 // One tile (raw words and the lane's byte lengths lw given) coded into the window `win`, from bit B & 127 (the
@@ -868,113 +793,14 @@ __device__ __forceinline__ uint32_t v1_tile_qwords(uint64_t B, uint32_t total)
   return ((uint32_t)(B & 127u) + total + 63u) / 64u + 2u;
 }
 
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile(FieldDesc F, Params p, const uint64_t* __restrict__ rbase,
-                                                           const uint32_t* __restrict__ lens8,
-                                                           uint32_t* __restrict__ out32, uint64_t* __restrict__ index,
-                                                           uint32_t index_shift, uint32_t ntiles,
-                                                           uint32_t* __restrict__ over)
-{
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];  // pair table rows 0..3 (lean-5 entries, row 3 empty)
-  __shared__ uint32_t rs[1024];    // window spread tables
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];  // the tile's code from bit base & 127 of its window
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t t = blockIdx.x;
-  // every load the tile needs is issued before anything waits (one memory round trip per workgroup): the input rows,
-  // the lane's byte lengths, the pair table, the tile's stream offsets
-  V1Raw<DT> raw;
-  raw.load(F, t, F.vec && (((uintptr_t)F.data) & 15u) == 0);
-  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  const uint64_t B = rbase[t];
-  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for k_encode1d_var_tile_big (over[0] = count)
-    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
-    return;
-  }
-  v1_tile_code<DT>(F, p, t, B, raw, lw, index, index_shift, tab, rs, win, scan_sh, &s_special);
-  v1_tile_store(t, B, total, win, out32, ntiles);
-}
-
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big(FieldDesc F, Params p,
-                                                               const uint64_t* __restrict__ rbase,
-                                                               const uint32_t* __restrict__ lens8,
-                                                               uint32_t* __restrict__ out32,
-                                                               uint64_t* __restrict__ index, uint32_t index_shift,
-                                                               uint32_t ntiles, const uint32_t* __restrict__ over)
-{
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t n = over[0];
-  if (blockIdx.x >= n) return;
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t t = over[1 + i];
-    const uint64_t B = rbase[t];
-    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-    v1_tile<DT>(F, p, t, B, total, lens8, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
-    __syncthreads();  // the window and scan slots are reused by the next tile
-  }
-}
-
-// The tile form's workspace: sums[ntiles], base[ntiles + 1] (uint64), the oversized-tile list (count + ntiles
-// uint32, rounded to 8 bytes), the byte lengths of whole tiles, then the totals of groups of 8 tiles.
-static inline uint64_t v1_list_words(uint64_t ntiles) { return (ntiles + 2) / 2; }  // uint64 words
-
-size_t var1d_tile_workspace_bytes(uint64_t nblocks)
-{
-  const uint64_t ntiles = (nblocks + V1TILE - 1) / V1TILE;
-  return (size_t)((2 * ntiles + 2 + v1_list_words(ntiles) + (ntiles + V1CT - 1) / V1CT) * 8 + ntiles * V1TILE);
-}
-
-hipError_t launch_encode1d_var_tile(const FieldDesc& F, const Params& p, uint32_t* out32, uint64_t* ws,
-                                    uint64_t* d_total, uint64_t* index, uint32_t index_shift, const uint64_t* d_base,
-                                    void* stream)
-{
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
-  uint64_t* sums = ws;
-  uint64_t* base = ws + ntiles;
-  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
-  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
-  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
-  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
-  if (F.dtype == DT_BF16) k_count1d_var_tile<DT_BF16><<<ncw, V1T, 0, st>>>(F, p, ntiles, sums, lens8, over, gsums);
-  else k_count1d_var_tile<DT_F32><<<ncw, V1T, 0, st>>>(F, p, ntiles, sums, lens8, over, gsums);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, d_base, st, gsums);
-  if (e != hipSuccess) return e;
-  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
-  if (F.dtype == DT_BF16) {
-    k_encode1d_var_tile<DT_BF16><<<ntiles, V1T, 0, st>>>(F, p, base, lens8, out32, index, index_shift, ntiles, over);
-    k_encode1d_var_tile_big<DT_BF16><<<nbig, V1T, 0, st>>>(F, p, base, lens8, out32, index, index_shift, ntiles,
-                                                           over);
-  } else {
-    k_encode1d_var_tile<DT_F32><<<ntiles, V1T, 0, st>>>(F, p, base, lens8, out32, index, index_shift, ntiles, over);
-    k_encode1d_var_tile_big<DT_F32><<<nbig, V1T, 0, st>>>(F, p, base, lens8, out32, index, index_shift, ntiles, over);
-  }
-  return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------- tile form with the residual
-// Error feedback at variable rate (gcow_encode_residual_device, include/gcow.h): the tile form above
+// Error feedback at variable rate (gcow_encode_residual_device, include/gcow.h): the tile form
 // on the field y = x + e (fp32; x fp32 or bf16, e fp32 or absent), whose code pass also writes e' = finite(y - yhat).
 // yhat needs no decoder: in this domain it is v1_decode_closed of the coefficients v1_prep hands the coder anyway
 // (the hook of v1_tile_code), so the residual costs one more row read in each pass and one row written.
-//   k_count1d_var_tile_resid       k_count1d_var_tile on y: the x rows and the e rows of tile i + PF are requested
-//                                  before tile i is counted; writes lens8 / sums / gsums, nothing to e_out
-//   k_encode1d_var_tile_resid      k_encode1d_var_tile on y, plus the tile's e' rows
-//   k_encode1d_var_tile_big_resid  the oversized tiles, as k_encode1d_var_tile_big
+//   count   on y: the x rows and the e rows of tile i + PF are requested before tile i is counted; writes lens8 /
+//           sums / gsums, nothing to e_out
+//   coders  on y, plus the tile's e' rows
 // e_in may be e_out: a lane reads the e rows of its own blocks only, and the e' rows it stores are those of its quad
 // of lanes (V1ResidOut::store_quad), computed from values all four have loaded -- so every row a wave writes it has
 // read before, and no other wave reads it. Every tile is coded (its e read and its e' written) exactly once, by the
@@ -1054,101 +880,6 @@ __device__ __forceinline__ void v1_wait_tiles_xe(v1_u4 (&x)[NX], v1_u4 (&e)[V1U]
   }
 }
 
-template <int DT_X, bool HASE>
-__global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid(FieldDesc F, Params p, const float* e_in,
-                                                                uint32_t ntiles, uint64_t* __restrict__ sums,
-                                                                uint32_t* __restrict__ lens8,
-                                                                uint32_t* __restrict__ nover,
-                                                                uint64_t* __restrict__ gsums)
-{
-  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
-  // k_count1d_var_tile's shape. Loads per lane and tile, in issue order: NX x rows (fp32: 4, bf16: 2), then with HASE
-  // the V1U = 4 e rows -- NT = 8 (fp32), 6 (bf16), or 4 / 2 without e. Nothing is stored inside the loop, so vmcnt
-  // counts loads only: once tile i's loads are issued, the operations issued after them are the loads of tiles
-  // i + 1 .. min(i + PF, V1CT - 1), k tiles of NT each, and tile i has landed at vmcnt(k NT) (at most 3 x 8 = 24 of
-  // the counter's 63).
-  __shared__ uint32_t red[V1CT][V1T / 64];
-  const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
-  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile_resid starts empty
-  const bool wide_ok = F.vec && v1_aligned16(F.data) && (!HASE || v1_aligned16(e_in));
-  constexpr int NX = V1Raw<DT_X>::N;                                  // 16-byte x loads per lane per tile
-  constexpr uint32_t TBX = V1TILE * (DT_X == DT_BF16 ? 8u : 16u);     // x bytes per tile
-  constexpr uint32_t TBE = V1TILE * 16u;                              // e bytes per tile
-  uint32_t packed[V1CT];
-  if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
-    const v1_v4i rsx = v1_rsrc((const char*)F.data + (size_t)t0 * TBX, V1CT * TBX);
-    const v1_v4i rse = v1_rsrc((const char*)e_in + (size_t)t0 * TBE, HASE ? V1CT * TBE : 0u);
-    constexpr uint32_t PF = V1_RESID_PF, RING = PF + 1;
-    v1_u4 bx[RING][NX], be[HASE ? RING : 1][V1U];
-    auto request = [&](uint32_t i) {
-#pragma unroll
-      for (int h = 0; h < NX; h++) bx[i % RING][h] = v1_ld16(i * TBX + (tid * NX + h) * 16u, rsx);
-      if constexpr (HASE) {
-#pragma unroll
-        for (uint32_t h = 0; h < V1U; h++) be[i % RING][h] = v1_ld16(i * TBE + (tid * V1U + h) * 16u, rse);
-      }
-    };
-#pragma unroll
-    for (uint32_t i = 0; i < PF && i < V1CT; i++) request(i);
-#pragma unroll
-    for (uint32_t i = 0; i < V1CT; i++) {
-      if (i + PF < V1CT) request(i + PF);
-      v1_wait_tiles_xe<NX, HASE>(bx[i % RING], be[HASE ? i % RING : 0], (i + PF < V1CT ? PF : V1CT - 1 - i));
-      V1Raw<DT_X> rx;
-      V1Raw<DT_F32> re, y;
-#pragma unroll
-      for (int h = 0; h < NX; h++) {
-        const v1_u4 v = bx[i % RING][h];
-        rx.w[h] = make_uint4(v.x, v.y, v.z, v.w);
-      }
-#pragma unroll
-      for (uint32_t h = 0; h < V1U; h++) {
-        if constexpr (HASE) {
-          const v1_u4 v = be[i % RING][h];
-          re.w[h] = make_uint4(v.x, v.y, v.z, v.w);
-        } else {
-          re.w[h] = make_uint4(0u, 0u, 0u, 0u);
-        }
-      }
-      v1_form_y<DT_X>(rx, re, y);
-      uint32_t lsum;
-      packed[i] = v1_count_tile<DT_F32, true>(F, p, y, t0 + i, lsum);
-      lsum = wave_sum_dpp(lsum);
-      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
-    }
-  } else {  // partial tiles, the padded last block, n % 4 != 0
-#pragma unroll
-    for (uint32_t i = 0; i < V1CT; i++) {
-      uint32_t lsum = 0;
-      packed[i] = 0;
-      if (t0 + i < ntiles) {
-        V1Raw<DT_F32> y;
-        v1_load_y<DT_X>(F, HASE ? e_in : nullptr, t0 + i, y);
-        packed[i] = v1_count_tile<DT_F32>(F, p, y, t0 + i, lsum);
-      }
-      lsum = wave_sum_dpp(lsum);
-      if ((tid & 63u) == 0) red[i][tid >> 6] = lsum;
-    }
-  }
-#pragma unroll
-  for (uint32_t i = 0; i < V1CT; i++)
-    if (t0 + i < ntiles) lens8[(size_t)(t0 + i) * V1T + tid] = packed[i];
-  __syncthreads();
-  if (tid < 64) {  // wave 0: the tile totals, and their sum for the scan's group totals
-    uint64_t tot = 0;
-    if (tid < V1CT && t0 + tid < ntiles) {
-#pragma unroll
-      for (uint32_t w = 0; w < V1T / 64; w++) tot += red[tid][w];
-      sums[t0 + tid] = tot;
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) {
-      const uint32_t lo = __shfl_xor((uint32_t)tot, o, 64), hi = __shfl_xor((uint32_t)(tot >> 32), o, 64);
-      tot += (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    if (tid == 0) gsums[blockIdx.x] = tot;
-  }
-}
 
 // The e' rows of one tile: whole rows go through a buffer whose range is the tile's whole blocks inside the field (a
 // row past it is dropped: padding blocks give no residual, nothing lands past e_out[n - 1]); the real values of the
@@ -1259,151 +990,39 @@ __device__ __forceinline__ void v1_tile_resid(const FieldDesc& F, const Params& 
   eo.store_quad(rows);
 }
 
-template <int DT_X>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_resid(FieldDesc F, Params p, const float* e_in, float* e_out,
-                                                                 const uint64_t* __restrict__ rbase,
-                                                                 const uint32_t* __restrict__ lens8,
-                                                                 uint32_t* __restrict__ out32,
-                                                                 uint64_t* __restrict__ index, uint32_t index_shift,
-                                                                 uint32_t ntiles, uint32_t* __restrict__ over)
-{
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t t = blockIdx.x;
-  // as in k_encode1d_var_tile, every load the tile needs is issued before anything waits: the x and e rows (all of
-  // the lane's e rows, before any e' store), the byte lengths, the pair table, the stream offsets
-  V1Raw<DT_F32> y;
-  v1_load_y<DT_X>(F, e_in, t, y);
-  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  const uint64_t B = rbase[t];
-  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel, nothing stored here
-    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
-    return;
-  }
-  v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
-}
+// ----------------------------------------------------------------------------------------- tile form: the kernels
+// Every kernel is a template over its parameter source PS (ParamsHost / ParamsDev, var1d_prep.h), called once at the
+// top. The count kernels count vmcnt by hand, so they take the parameters WAITED: a device word is loaded and waited
+// for before the ring's first raw buffer load is issued, and as a scalar load it is none vmcnt counts (the rule is
+// stated at fitted_params_dev). The coders' loads are all compiler-managed; there the word's load goes out with the
+// tile's others and is first used after them.
+// The field's own values (k_count1d_var_tile, k_encode1d_var_tile, _big) and y = x + e (the same names with _resid)
+// keep a body each where their text differs -- how a tile's loads are requested, waited for and formed into values,
+// and what is called around v1_tile_code: folded into one body, the compiler schedules the field's kernels
+// differently (the same instructions in another order, other registers), and so it does even when the count
+// kernels' stores and totals or the oversized-tile test move into a function of their own: those stay in the kernels'
+// text. Written once are the coders' LDS and tables (v1_lds), the launcher and the workspace layout.
+static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
 
-template <int DT_X>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid(FieldDesc F, Params p, const float* e_in,
-                                                                     float* e_out, const uint64_t* __restrict__ rbase,
-                                                                     const uint32_t* __restrict__ lens8,
-                                                                     uint32_t* __restrict__ out32,
-                                                                     uint64_t* __restrict__ index,
-                                                                     uint32_t index_shift, uint32_t ntiles,
-                                                                     const uint32_t* __restrict__ over)
+template <int DT, class PS>
+__global__ __launch_bounds__(V1T) void k_count1d_var_tile(FieldDesc F, PS ps, uint32_t ntiles,
+                                                          uint64_t* __restrict__ sums, uint32_t* __restrict__ lens8,
+                                                          uint32_t* __restrict__ nover, uint64_t* __restrict__ gsums)
 {
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t n = over[0];
-  if (blockIdx.x >= n) return;
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t t = over[1 + i];
-    const uint64_t B = rbase[t];
-    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-    V1Raw<DT_F32> y;
-    v1_load_y<DT_X>(F, e_in, t, y);
-    const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
-    v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh,
-                  &s_special);
-    __syncthreads();  // the window and scan slots are reused by the next tile
-  }
-}
-
-template <int DT_X>
-static hipError_t launch_resid1d_var_t(const FieldDesc& F, const Params& p, const float* e_in, float* e_out,
-                                       uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
-                                       uint32_t index_shift, hipStream_t st)
-{
-  // the tile form's workspace layout (launch_encode1d_var_tile)
-  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
-  uint64_t* sums = ws;
-  uint64_t* base = ws + ntiles;
-  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
-  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
-  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
-  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
-  if (e_in) k_count1d_var_tile_resid<DT_X, true><<<ncw, V1T, 0, st>>>(F, p, e_in, ntiles, sums, lens8, over, gsums);
-  else k_count1d_var_tile_resid<DT_X, false><<<ncw, V1T, 0, st>>>(F, p, nullptr, ntiles, sums, lens8, over, gsums);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
-  if (e != hipSuccess) return e;
-  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
-  k_encode1d_var_tile_resid<DT_X><<<ntiles, V1T, 0, st>>>(F, p, e_in, e_out, base, lens8, out32, index, index_shift,
-                                                          ntiles, over);
-  k_encode1d_var_tile_big_resid<DT_X><<<nbig, V1T, 0, st>>>(F, p, e_in, e_out, base, lens8, out32, index, index_shift,
-                                                            ntiles, over);
-  return hipGetLastError();
-}
-
-hipError_t launch_encode_resid1d_var(const void* x, int x_dtype, uint64_t nvals, const Params& p, const float* e_in,
-                                     float* e_out, uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
-                                     uint32_t index_shift, void* stream)
-{
-  FieldDesc F = {};
-  F.data = x;
-  F.n[0] = nvals;
-  F.n[1] = F.n[2] = F.n[3] = 1;
-  F.s[0] = 1;
-  F.nblocks = F.bx = (uint32_t)((nvals + 3) / 4);
-  F.by = F.bz = F.bw = 1;
-  F.dims = 1;
-  F.dtype = (uint32_t)x_dtype;
-  F.vec = ((uintptr_t)x % (x_dtype == DT_BF16 ? 8u : 16u)) == 0 ? 1u : 0u;
-  if (x_dtype == DT_BF16)
-    return launch_resid1d_var_t<DT_BF16>(F, p, e_in, e_out, out32, ws, d_total, index, index_shift,
-                                         (hipStream_t)stream);
-  return launch_resid1d_var_t<DT_F32>(F, p, e_in, e_out, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------- tile form, minexp from device memory
-// gcow_encode_fitted_device (include/gcow.h): the tile form above under
-// Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernels run -- a fit that a kernel earlier in the
-// stream wrote (k_rate_table_fit) needs no host read in between, and a captured graph follows the data it is replayed
-// on. Nothing on the host depends on minexp: the workspace layout, the scan and the oversized-tile list are the tile
-// form's own. Each kernel builds its Params once at the top (fitted_params_dev, var1d_prep.h) and runs the tile
-// form's device functions unchanged.
-//   k_count1d_var_tile_fitted      k_count1d_var_tile's body. Its ring of raw buffer loads is waited for with
-//                                  hand-counted vmcnt; the minexp word is loaded AND waited for before the ring's
-//                                  first load is issued (fitted_params_dev<true> ends in an asm that takes the
-//                                  value in an SGPR), and it is a scalar load, which vmcnt does not count: the counts of
-//                                  v1_wait_tiles hold as they stand. The cost is one scalar-cache round trip per
-//                                  workgroup of 8 tiles ahead of its loads.
-//   k_encode1d_var_tile_fitted     k_encode1d_var_tile: the word's load is issued with the tile's other loads (all
-//   k_encode1d_var_tile_big_fitted compiler-managed there, no hand-counted wait) and first used after them.
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_count1d_var_tile_fitted(FieldDesc F, uint32_t maxprec,
-                                                                 const int32_t* __restrict__ d_minexp, uint32_t ntiles,
-                                                                 uint64_t* __restrict__ sums,
-                                                                 uint32_t* __restrict__ lens8,
-                                                                 uint32_t* __restrict__ nover,
-                                                                 uint64_t* __restrict__ gsums)
-{
-  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
-  const Params p = fitted_params_dev<true>(maxprec, d_minexp);  // loaded and waited for: nothing outstanding here
+  // V1CT consecutive tiles per workgroup. Full contiguous tiles are software-pipelined: tile i + 1's raw buffer loads
+  // are issued before tile i is counted (hand-counted waits), and nothing is stored until the loop is done -- the
+  // workgroups of a one-shot grid otherwise run in lock step, all loading and then all computing.
+  const Params p = ps.template get<true>();  // a device word is loaded and waited for: nothing outstanding here
   __shared__ uint32_t red[V1CT][V1T / 64];
   const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
-  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile_fitted starts empty
+  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile starts empty
   const bool wide_ok = F.vec && (((uintptr_t)F.data) & 15u) == 0;
   constexpr int NL = V1Raw<DT>::N;                                 // 16-byte loads per lane per tile
   constexpr uint32_t TB = V1TILE * (DT == DT_BF16 ? 8u : 16u);     // bytes per tile
   uint32_t packed[V1CT];
   if (wide_ok && (uint64_t)(t0 + V1CT) * V1TILE <= F.n[0] / 4) {
     const v1_v4i rs = v1_rsrc((const char*)F.data + (size_t)t0 * TB, V1CT * TB);
-    // k_count1d_var_tile's ring: tile i + PF is requested before tile i is counted
+    // a ring of PF + 1 tiles: tile i + PF is requested before tile i is counted, so PF tiles of loads stay in flight
     constexpr uint32_t PF = V1_COUNT_PF, RING = PF + 1;
     v1_u4 buf[RING][NL];
 #pragma unroll
@@ -1463,129 +1082,22 @@ __global__ __launch_bounds__(V1T) void k_count1d_var_tile_fitted(FieldDesc F, ui
   }
 }
 
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_fitted(FieldDesc F, uint32_t maxprec,
-                                                                  const int32_t* __restrict__ d_minexp,
-                                                                  const uint64_t* __restrict__ rbase,
-                                                                  const uint32_t* __restrict__ lens8,
-                                                                  uint32_t* __restrict__ out32,
-                                                                  uint64_t* __restrict__ index, uint32_t index_shift,
-                                                                  uint32_t ntiles, uint32_t* __restrict__ over)
+template <int DT_X, bool HASE, class PS>
+__global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid(FieldDesc F, PS ps, const float* e_in, uint32_t ntiles,
+                                                                uint64_t* __restrict__ sums,
+                                                                uint32_t* __restrict__ lens8,
+                                                                uint32_t* __restrict__ nover,
+                                                                uint64_t* __restrict__ gsums)
 {
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t t = blockIdx.x;
-  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
-  // as in k_encode1d_var_tile, every load the tile needs is issued before anything else waits
-  V1Raw<DT> raw;
-  raw.load(F, t, F.vec && (((uintptr_t)F.data) & 15u) == 0);
-  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  const uint64_t B = rbase[t];
-  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for k_encode1d_var_tile_big_fitted (over[0] = count)
-    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
-    return;
-  }
-  v1_tile_code<DT>(F, p, t, B, raw, lw, index, index_shift, tab, rs, win, scan_sh, &s_special);
-  v1_tile_store(t, B, total, win, out32, ntiles);
-}
-
-template <int DT>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_fitted(FieldDesc F, uint32_t maxprec,
-                                                                      const int32_t* __restrict__ d_minexp,
-                                                                      const uint64_t* __restrict__ rbase,
-                                                                      const uint32_t* __restrict__ lens8,
-                                                                      uint32_t* __restrict__ out32,
-                                                                      uint64_t* __restrict__ index,
-                                                                      uint32_t index_shift, uint32_t ntiles,
-                                                                      const uint32_t* __restrict__ over)
-{
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
-  const uint32_t n = over[0];
-  if (blockIdx.x >= n) return;
-  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-    const uint32_t t = over[1 + i];
-    const uint64_t B = rbase[t];
-    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-    v1_tile<DT>(F, p, t, B, total, lens8, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
-    __syncthreads();  // the window and scan slots are reused by the next tile
-  }
-}
-
-template <int DT>
-static hipError_t launch_fitted1d_t(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp, uint32_t* out32,
-                                    uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
-                                    hipStream_t st)
-{
-  // the tile form's workspace layout (launch_encode1d_var_tile)
-  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
-  uint64_t* sums = ws;
-  uint64_t* base = ws + ntiles;
-  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
-  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
-  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
-  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
-  k_count1d_var_tile_fitted<DT><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, ntiles, sums, lens8, over, gsums);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
-  if (e != hipSuccess) return e;
-  const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
-  k_encode1d_var_tile_fitted<DT><<<ntiles, V1T, 0, st>>>(F, maxprec, d_minexp, base, lens8, out32, index, index_shift,
-                                                         ntiles, over);
-  k_encode1d_var_tile_big_fitted<DT><<<nbig, V1T, 0, st>>>(F, maxprec, d_minexp, base, lens8, out32, index,
-                                                           index_shift, ntiles, over);
-  return hipGetLastError();
-}
-
-hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
-                                           uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
-                                           uint32_t index_shift, void* stream)
-{
-  if (F.dtype == DT_BF16)
-    return launch_fitted1d_t<DT_BF16>(F, maxprec, d_minexp, out32, ws, d_total, index, index_shift,
-                                      (hipStream_t)stream);
-  return launch_fitted1d_t<DT_F32>(F, maxprec, d_minexp, out32, ws, d_total, index, index_shift, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------- tile form with the residual, minexp from device memory
-// gcow_encode_residual_fitted_device (include/gcow.h): the residual tile form under
-// Params{1, 16658, maxprec, clamp(*d_minexp)}, as the kernels above are the tile form's. Each kernel builds its Params
-// at the top and runs the residual device functions (v1_form_y, v1_load_y, v1_tile_resid, V1ResidOut) unchanged.
-//   k_count1d_var_tile_resid_fitted      k_count1d_var_tile_resid's body; the word is loaded and waited for before the
-//                                        ring's first raw buffer load (fitted_params_dev<true>), so the hand-counted
-//                                        vmcnt of v1_wait_tiles_xe holds as it stands.
-//   k_encode1d_var_tile_resid_fitted     k_encode1d_var_tile_resid: the word's load goes out with the tile's others.
-//   k_encode1d_var_tile_big_resid_fitted the oversized tiles.
-template <int DT_X, bool HASE>
-__global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid_fitted(FieldDesc F, uint32_t maxprec,
-                                                                       const int32_t* __restrict__ d_minexp,
-                                                                       const float* e_in, uint32_t ntiles,
-                                                                       uint64_t* __restrict__ sums,
-                                                                       uint32_t* __restrict__ lens8,
-                                                                       uint32_t* __restrict__ nover,
-                                                                       uint64_t* __restrict__ gsums)
-{
-  static_assert(V1CT == 8, "the scan's group totals (gsums) cover 8 tiles");
-  const Params p = fitted_params_dev<true>(maxprec, d_minexp);  // loaded and waited for: nothing outstanding here
-  // k_count1d_var_tile_resid's loop and its load count per tile (NT = NX + V1U with e, NX without)
+  // k_count1d_var_tile's shape. Loads per lane and tile, in issue order: NX x rows (fp32: 4, bf16: 2), then with HASE
+  // the V1U = 4 e rows -- NT = 8 (fp32), 6 (bf16), or 4 / 2 without e. Nothing is stored inside the loop, so vmcnt
+  // counts loads only: once tile i's loads are issued, the operations issued after them are the loads of tiles
+  // i + 1 .. min(i + PF, V1CT - 1), k tiles of NT each, and tile i has landed at vmcnt(k NT) (at most 3 x 8 = 24 of
+  // the counter's 63).
+  const Params p = ps.template get<true>();  // a device word is loaded and waited for: nothing outstanding here
   __shared__ uint32_t red[V1CT][V1T / 64];
   const uint32_t tid = threadIdx.x, t0 = blockIdx.x * V1CT;
-  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of the encode kernel starts empty
+  if (blockIdx.x == 0 && tid == 0) *nover = 0u;  // the oversized-tile list of k_encode1d_var_tile_resid starts empty
   const bool wide_ok = F.vec && v1_aligned16(F.data) && (!HASE || v1_aligned16(e_in));
   constexpr int NX = V1Raw<DT_X>::N;                                  // 16-byte x loads per lane per tile
   constexpr uint32_t TBX = V1TILE * (DT_X == DT_BF16 ? 8u : 16u);     // x bytes per tile
@@ -1666,62 +1178,112 @@ __global__ __launch_bounds__(V1T) void k_count1d_var_tile_resid_fitted(FieldDesc
   }
 }
 
-template <int DT_X>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_resid_fitted(FieldDesc F, uint32_t maxprec,
-                                                                        const int32_t* __restrict__ d_minexp,
-                                                                        const float* e_in, float* e_out,
-                                                                        const uint64_t* __restrict__ rbase,
-                                                                        const uint32_t* __restrict__ lens8,
-                                                                        uint32_t* __restrict__ out32,
-                                                                        uint64_t* __restrict__ index,
-                                                                        uint32_t index_shift, uint32_t ntiles,
-                                                                        uint32_t* __restrict__ over)
+// The coders' LDS with a window of Q qwords, the pair table (rows 0..3, lean-5 entries, row 3 empty) and the window
+// spread tables staged.
+struct V1Lds {
+  uint32_t *tab, *rs;
+  uint64_t* win;  // the tile's code from bit base & 127 of its window
+  uint32_t *scan_sh, *s_special;
+};
+template <uint32_t Q>
+__device__ __forceinline__ V1Lds v1_lds()
 {
   __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
   __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1QS];
+  __shared__ __attribute__((aligned(16))) uint64_t win[Q];
   __shared__ uint32_t scan_sh[V1T / 64];
   __shared__ uint32_t s_special;
-  const uint32_t t = blockIdx.x;
-  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
-  // as in k_encode1d_var_tile_resid, every load the tile needs is issued before anything else waits
-  V1Raw<DT_F32> y;
-  v1_load_y<DT_X>(F, e_in, t, y);
-  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
   stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
 #pragma unroll
   for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  return V1Lds{tab, rs, win, scan_sh, &s_special};
+}
+
+template <int DT, class PS>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile(FieldDesc F, PS ps, const uint64_t* __restrict__ rbase,
+                                                           const uint32_t* __restrict__ lens8,
+                                                           uint32_t* __restrict__ out32, uint64_t* __restrict__ index,
+                                                           uint32_t index_shift, uint32_t ntiles,
+                                                           uint32_t* __restrict__ over)
+{
+  const uint32_t t = blockIdx.x;
+  const Params p = ps.template get<false>();
+  // every load the tile needs is issued before anything waits (one memory round trip per workgroup): the input rows,
+  // the lane's byte lengths, the pair table, the tile's stream offsets
+  V1Raw<DT> raw;
+  raw.load(F, t, F.vec && (((uintptr_t)F.data) & 15u) == 0);
+  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+  const V1Lds L = v1_lds<V1QS>();
   const uint64_t B = rbase[t];
   const uint32_t total = (uint32_t)(rbase[t + 1] - B);
-  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel, nothing stored here
+  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel (over[0] = count), nothing stored
     if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
     return;
   }
-  v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh, &s_special);
+  v1_tile_code<DT>(F, p, t, B, raw, lw, index, index_shift, L.tab, L.rs, L.win, L.scan_sh, L.s_special);
+  v1_tile_store(t, B, total, L.win, out32, ntiles);
 }
 
-template <int DT_X>
-__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid_fitted(FieldDesc F, uint32_t maxprec,
-                                                                            const int32_t* __restrict__ d_minexp,
-                                                                            const float* e_in, float* e_out,
-                                                                            const uint64_t* __restrict__ rbase,
-                                                                            const uint32_t* __restrict__ lens8,
-                                                                            uint32_t* __restrict__ out32,
-                                                                            uint64_t* __restrict__ index,
-                                                                            uint32_t index_shift, uint32_t ntiles,
-                                                                            const uint32_t* __restrict__ over)
+template <int DT, class PS>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big(FieldDesc F, PS ps, const uint64_t* __restrict__ rbase,
+                                                               const uint32_t* __restrict__ lens8,
+                                                               uint32_t* __restrict__ out32,
+                                                               uint64_t* __restrict__ index, uint32_t index_shift,
+                                                               uint32_t ntiles, const uint32_t* __restrict__ over)
 {
-  __shared__ __attribute__((aligned(16))) uint32_t tab[V1TAB];
-  __shared__ uint32_t rs[1024];
-  __shared__ __attribute__((aligned(16))) uint64_t win[V1Q + 2];
-  __shared__ uint32_t scan_sh[V1T / 64];
-  __shared__ uint32_t s_special;
   const uint32_t n = over[0];
   if (blockIdx.x >= n) return;
-  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
-  stage_table<V1T, V1TAB>(tab, g_plane_tab_var.v);
-#pragma unroll
-  for (uint32_t i = 0; i < 1024 / V1T; i++) rs[threadIdx.x + V1T * i] = rspread_entry(threadIdx.x + V1T * i);
+  const Params p = ps.template get<false>();
+  const V1Lds L = v1_lds<V1Q + 2>();
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t t = over[1 + i];
+    const uint64_t B = rbase[t];
+    const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+    v1_tile<DT>(F, p, t, B, total, lens8, out32, index, index_shift, ntiles, L.tab, L.rs, L.win, L.scan_sh,
+                L.s_special);
+    __syncthreads();  // the window and scan slots are reused by the next tile
+  }
+}
+
+template <int DT_X, class PS>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_resid(FieldDesc F, PS ps, const float* e_in, float* e_out,
+                                                                 const uint64_t* __restrict__ rbase,
+                                                                 const uint32_t* __restrict__ lens8,
+                                                                 uint32_t* __restrict__ out32,
+                                                                 uint64_t* __restrict__ index, uint32_t index_shift,
+                                                                 uint32_t ntiles, uint32_t* __restrict__ over)
+{
+  const uint32_t t = blockIdx.x;
+  const Params p = ps.template get<false>();
+  // as in k_encode1d_var_tile, every load the tile needs is issued before anything waits: the x and e rows (all of
+  // the lane's e rows, before any e' store), the byte lengths, the pair table, the stream offsets
+  V1Raw<DT_F32> y;
+  v1_load_y<DT_X>(F, e_in, t, y);
+  const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
+  const V1Lds L = v1_lds<V1QS>();
+  const uint64_t B = rbase[t];
+  const uint32_t total = (uint32_t)(rbase[t + 1] - B);
+  if (v1_tile_qwords(B, total) > V1QS) {  // oversized: listed for the _big kernel (over[0] = count), nothing stored
+    if (threadIdx.x == 0) over[1 + atomicAdd(over, 1u)] = t;
+    return;
+  }
+  v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, L.tab, L.rs, L.win, L.scan_sh,
+                L.s_special);
+}
+
+template <int DT_X, class PS>
+__global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid(FieldDesc F, PS ps, const float* e_in,
+                                                                     float* e_out, const uint64_t* __restrict__ rbase,
+                                                                     const uint32_t* __restrict__ lens8,
+                                                                     uint32_t* __restrict__ out32,
+                                                                     uint64_t* __restrict__ index,
+                                                                     uint32_t index_shift, uint32_t ntiles,
+                                                                     const uint32_t* __restrict__ over)
+{
+  const uint32_t n = over[0];
+  if (blockIdx.x >= n) return;
+  const Params p = ps.template get<false>();
+  const V1Lds L = v1_lds<V1Q + 2>();
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
     const uint32_t t = over[1 + i];
     const uint64_t B = rbase[t];
@@ -1729,49 +1291,80 @@ __global__ __launch_bounds__(V1T) void k_encode1d_var_tile_big_resid_fitted(Fiel
     V1Raw<DT_F32> y;
     v1_load_y<DT_X>(F, e_in, t, y);
     const uint32_t lw = lens8[(size_t)t * V1T + threadIdx.x];
-    v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, tab, rs, win, scan_sh,
-                  &s_special);
+    v1_tile_resid(F, p, e_out, t, B, total, y, lw, out32, index, index_shift, ntiles, L.tab, L.rs, L.win, L.scan_sh,
+                  L.s_special);
     __syncthreads();  // the window and scan slots are reused by the next tile
   }
 }
 
-template <int DT_X>
-static hipError_t launch_resid1d_var_fitted_t(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
-                                              const float* e_in, float* e_out, uint32_t* out32, uint64_t* ws,
-                                              uint64_t* d_total, uint64_t* index, uint32_t index_shift, hipStream_t st)
+// ------------------------------------------------------------------------- tile form: the workspace and the launchers
+// The workspace: sums[ntiles], base[ntiles + 1] (uint64), the oversized-tile list (count + ntiles uint32, rounded to 8
+// bytes), the byte lengths of whole tiles, then the totals of groups of V1CT tiles.
+struct V1Workspace {
+  uint32_t ntiles;
+  size_t o_base, o_over, o_lens8, o_gsums, words;  // in uint64 words
+  explicit V1Workspace(uint64_t nblocks) : ntiles((uint32_t)((nblocks + V1TILE - 1) / V1TILE))
+  {
+    static_assert(V1T % 2 == 0, "a tile's byte lengths are whole uint64 words");
+    o_base = ntiles;
+    o_over = o_base + ntiles + 2;
+    o_lens8 = o_over + (ntiles + 2) / 2;
+    o_gsums = o_lens8 + (size_t)ntiles * (V1T / 2);
+    words = o_gsums + (ntiles + V1CT - 1) / V1CT;
+  }
+};
+
+size_t var1d_tile_workspace_bytes(uint64_t nblocks) { return V1Workspace(nblocks).words * 8; }
+
+// count -> scan -> coder -> oversized tiles, of the field's values (resid false: e_in, e_out unused) or of y = x + e
+// (e_in may be null) with the residual written to e_out.
+template <int DT, class PS>
+static hipError_t v1_launch_tile(const FieldDesc& F, const PS& ps, bool resid, const float* e_in, float* e_out,
+                                 uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                 uint32_t index_shift, const uint64_t* d_base, hipStream_t st)
 {
-  // the tile form's workspace layout (launch_encode1d_var_tile)
-  const uint32_t ntiles = (uint32_t)((F.nblocks + V1TILE - 1) / V1TILE);
-  uint64_t* sums = ws;
-  uint64_t* base = ws + ntiles;
-  uint32_t* over = (uint32_t*)(ws + 2 * (size_t)ntiles + 2);
-  uint32_t* lens8 = (uint32_t*)(ws + 2 * (size_t)ntiles + 2 + v1_list_words(ntiles));
-  uint64_t* gsums = (uint64_t*)(lens8 + (size_t)ntiles * V1T);
-  const uint32_t ncw = (ntiles + V1CT - 1) / V1CT;
-  if (e_in)
-    k_count1d_var_tile_resid_fitted<DT_X, true><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, ntiles, sums, lens8,
-                                                                     over, gsums);
+  const V1Workspace W(F.nblocks);
+  const uint32_t ntiles = W.ntiles, ncw = (ntiles + V1CT - 1) / V1CT;
+  uint64_t *sums = ws, *base = ws + W.o_base, *gsums = ws + W.o_gsums;
+  uint32_t *over = (uint32_t*)(ws + W.o_over), *lens8 = (uint32_t*)(ws + W.o_lens8);
+  if (!resid)
+    k_count1d_var_tile<DT, PS><<<ncw, V1T, 0, st>>>(F, ps, ntiles, sums, lens8, over, gsums);
+  else if (e_in)
+    k_count1d_var_tile_resid<DT, true, PS><<<ncw, V1T, 0, st>>>(F, ps, e_in, ntiles, sums, lens8, over, gsums);
   else
-    k_count1d_var_tile_resid_fitted<DT_X, false><<<ncw, V1T, 0, st>>>(F, maxprec, d_minexp, nullptr, ntiles, sums,
-                                                                      lens8, over, gsums);
+    k_count1d_var_tile_resid<DT, false, PS><<<ncw, V1T, 0, st>>>(F, ps, nullptr, ntiles, sums, lens8, over, gsums);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, nullptr, st, gsums);
+  e = launch_scan_ranges(sums, ntiles, base, d_total, out32, d_base, st, gsums);
   if (e != hipSuccess) return e;
   const uint32_t nbig = std::min(ntiles, 1280u);  // grid-stride workgroups of the oversized-tile pass (5 per CU)
-  k_encode1d_var_tile_resid_fitted<DT_X><<<ntiles, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, e_out, base, lens8, out32,
-                                                                 index, index_shift, ntiles, over);
-  k_encode1d_var_tile_big_resid_fitted<DT_X><<<nbig, V1T, 0, st>>>(F, maxprec, d_minexp, e_in, e_out, base, lens8,
-                                                                   out32, index, index_shift, ntiles, over);
+  if (!resid) {
+    k_encode1d_var_tile<DT, PS><<<ntiles, V1T, 0, st>>>(F, ps, base, lens8, out32, index, index_shift, ntiles, over);
+    k_encode1d_var_tile_big<DT, PS><<<nbig, V1T, 0, st>>>(F, ps, base, lens8, out32, index, index_shift, ntiles, over);
+  } else {
+    k_encode1d_var_tile_resid<DT, PS><<<ntiles, V1T, 0, st>>>(F, ps, e_in, e_out, base, lens8, out32, index,
+                                                              index_shift, ntiles, over);
+    k_encode1d_var_tile_big_resid<DT, PS><<<nbig, V1T, 0, st>>>(F, ps, e_in, e_out, base, lens8, out32, index,
+                                                                index_shift, ntiles, over);
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t nvals, uint32_t maxprec,
-                                            const int32_t* d_minexp, const float* e_in, float* e_out, uint32_t* out32,
-                                            uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
-                                            void* stream)
+template <class PS>
+static hipError_t v1_launch(const FieldDesc& F, const PS& ps, bool resid, const float* e_in, float* e_out,
+                            uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
+                            const uint64_t* d_base, void* stream)
 {
-  FieldDesc F = {};  // launch_encode_resid1d_var's descriptor
+  hipStream_t st = (hipStream_t)stream;
+  if (F.dtype == DT_BF16)
+    return v1_launch_tile<DT_BF16>(F, ps, resid, e_in, e_out, out32, ws, d_total, index, index_shift, d_base, st);
+  return v1_launch_tile<DT_F32>(F, ps, resid, e_in, e_out, out32, ws, d_total, index, index_shift, d_base, st);
+}
+
+// x as a contiguous 1-D field: what the residual entry points are given in place of a FieldDesc
+static FieldDesc v1_field1d(const void* x, int x_dtype, uint64_t nvals)
+{
+  FieldDesc F = {};
   F.data = x;
   F.n[0] = nvals;
   F.n[1] = F.n[2] = F.n[3] = 1;
@@ -1781,11 +1374,44 @@ hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t
   F.dims = 1;
   F.dtype = (uint32_t)x_dtype;
   F.vec = ((uintptr_t)x % (x_dtype == DT_BF16 ? 8u : 16u)) == 0 ? 1u : 0u;
-  if (x_dtype == DT_BF16)
-    return launch_resid1d_var_fitted_t<DT_BF16>(F, maxprec, d_minexp, e_in, e_out, out32, ws, d_total, index,
-                                                index_shift, (hipStream_t)stream);
-  return launch_resid1d_var_fitted_t<DT_F32>(F, maxprec, d_minexp, e_in, e_out, out32, ws, d_total, index, index_shift,
-                                             (hipStream_t)stream);
+  return F;
+}
+
+hipError_t launch_encode1d_var_tile(const FieldDesc& F, const Params& p, uint32_t* out32, uint64_t* ws,
+                                    uint64_t* d_total, uint64_t* index, uint32_t index_shift, const uint64_t* d_base,
+                                    void* stream)
+{
+  return v1_launch(F, ParamsHost{p}, false, nullptr, nullptr, out32, ws, d_total, index, index_shift, d_base, stream);
+}
+
+// gcow_encode_fitted_device (include/gcow.h): the tile form under
+// Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernels run -- a fit that a kernel earlier in the
+// stream wrote (k_rate_table_fit) needs no host read in between, and a captured graph follows the data it is replayed
+// on. Nothing on the host depends on minexp: the workspace layout, the scan and the oversized-tile list are the same.
+hipError_t launch_encode1d_var_tile_fitted(const FieldDesc& F, uint32_t maxprec, const int32_t* d_minexp,
+                                           uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                           uint32_t index_shift, void* stream)
+{
+  return v1_launch(F, ParamsDev{maxprec, d_minexp}, false, nullptr, nullptr, out32, ws, d_total, index, index_shift,
+                   nullptr, stream);
+}
+
+hipError_t launch_encode_resid1d_var(const void* x, int x_dtype, uint64_t nvals, const Params& p, const float* e_in,
+                                     float* e_out, uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                     uint32_t index_shift, void* stream)
+{
+  return v1_launch(v1_field1d(x, x_dtype, nvals), ParamsHost{p}, true, e_in, e_out, out32, ws, d_total, index,
+                   index_shift, nullptr, stream);
+}
+
+// gcow_encode_residual_fitted_device (include/gcow.h): the residual form under the device word.
+hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t nvals, uint32_t maxprec,
+                                            const int32_t* d_minexp, const float* e_in, float* e_out, uint32_t* out32,
+                                            uint64_t* ws, uint64_t* d_total, uint64_t* index, uint32_t index_shift,
+                                            void* stream)
+{
+  return v1_launch(v1_field1d(x, x_dtype, nvals), ParamsDev{maxprec, d_minexp}, true, e_in, e_out, out32, ws, d_total,
+                   index, index_shift, nullptr, stream);
 }
 
 }  // namespace gcow

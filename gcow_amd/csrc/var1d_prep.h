@@ -154,4 +154,25 @@ __device__ __forceinline__ Params fitted_params_dev(uint32_t maxprec, const int3
   return Params{1u, 16658u, maxprec, m};
 }
 
+// Where a kernel's parameter set comes from: a template parameter of the kernels that exist for both cases, passed by
+// value as a kernel argument. The kernel calls get once at its top -- with WAITED = true, ahead of its first asm load,
+// where it counts vmcnt by hand (the rule above).
+struct ParamsHost {  // the launch's own Params
+  Params p;
+  template <bool WAITED>
+  __device__ __forceinline__ Params get() const
+  {
+    return p;
+  }
+};
+struct ParamsDev {  // accuracy mode at the minexp word in device memory
+  uint32_t maxprec;
+  const int32_t* d_minexp;
+  template <bool WAITED>
+  __device__ __forceinline__ Params get() const
+  {
+    return fitted_params_dev<WAITED>(maxprec, d_minexp);
+  }
+};
+
 }  // namespace gcow
