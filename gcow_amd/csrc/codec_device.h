@@ -59,8 +59,10 @@ __device__ __forceinline__ uint64_t lowmask64(uint32_t n) { return n >= 64 ? ~0u
 // latency per iteration (10-20 of them per workgroup in the decoders before this was changed).
 typedef unsigned int st_v4u __attribute__((ext_vector_type(4)));
 
-// nbytes (<= MAXC * 16) bytes from src (16-byte aligned) to dst[0 .. MAXC) as 16-byte chunks; chunks past nbytes read
-// zero (buffer range check), so every lane issues the same loads. T threads.
+// nbytes (<= MAXC * 16) bytes from src to dst[0 .. MAXC) (16-byte aligned LDS) as 16-byte chunks; chunks past nbytes
+// read zero (buffer range check), so every lane issues the same loads. T threads. src needs 4-byte alignment only (a
+// buffer load): the decoders' spans start on a 16-byte boundary relative to the stream pointer, which may itself lie
+// 8 bytes off one (include/gcow.h; tests/test_gpu_decode_contract.py test_stream_pointer_at_an_odd_word).
 template <uint32_t T, uint32_t MAXC>
 __device__ __forceinline__ void stage_lds16(void* dst, const void* src, uint32_t nbytes)
 {

@@ -561,6 +561,28 @@ gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxpre
  * in_bytes may be the buffer's capacity; given the stream's own length (ceil(bits / 64) words), the 1-D
  * variable-rate decoder sizes its LDS stage from the stream's average bits per block (more waves for compressible
  * streams; the result is the same either way).
+ *
+ * The decoders' contract (gcow_decode_device, gcow_decode_device_at; tests/test_gpu_decode_contract.py pins it):
+ *   - After the stream: ANYTHING. The bits of the stream's last word above its last bit and every word after it
+ *     inside in_bytes are unspecified (the encoders say the same of the words up to their capacity, and a reused
+ *     buffer keeps a longer stream's words there). The decoders look past a block's last bit -- 64-bit windows, the
+ *     three 32-bit words of the LDS readers, staged spans that run to in_bytes -- and no value depends on what they
+ *     see there.
+ *   - Readable memory: d_in must be readable for ONE 64-bit word past the word that holds the stream's last bit,
+ *     ceil((bit_offset + bits) / 64) + 1 words in all, whatever in_bytes says: the global-memory readers (BitReader,
+ *     GlobalWindow) take the 64 bits at a bit position inside a block from its word and, off a word boundary, the
+ *     next one. The staged kernels copy a workgroup's span into LDS, never past in_bytes / 8 words, and zero-fill the
+ *     LDS behind it; what their readers take further out (up to three 32-bit words past a block's last bit) comes
+ *     from there. The whole-word fixed-rate kernels load the blocks' own words only. in_bytes must not exceed the
+ *     readable size; in_bytes == 0 means unknown (nothing is staged).
+ *   - d_in and d_index are arrays of uint64: 8-byte aligned, no more. Staged spans start on a 16-byte boundary
+ *     relative to d_in, and the 16-byte loads that copy them are buffer loads, which need 4-byte alignment.
+ *   - field->data: any element strides, negative ones included (data then points at the element with index 0), at
+ *     any element-aligned address. Rows that are contiguous and 16-byte aligned (fp32; 8 bytes for bf16) are written
+ *     with vector stores, everything else value by value; nothing outside the field's elements is written.
+ *   - index_stride: every power of two from 1 to 256 (one entry per index_stride blocks, gcow_index_entries of them;
+ *     a stride above the block count is one entry). A 4-D field uses its index at stride 1 only: at any other stride
+ *     d_index is ignored (never read) and the stream is walked in order, as with d_index == NULL.
  */
 gcow_status gcow_decode_device(const zfp_input* field, const gcow_params* p, const void* d_in, size_t in_bytes,
                                const uint64_t* d_index, uint32_t index_stride, void* hip_stream);
@@ -594,6 +616,10 @@ gcow_status gcow_stitch_shards_device(uint64_t* d_dst, uint64_t dst_words, const
  * maxbits >= 160 take the closed-form decoder, others the generic one) and every stream's block index (index_stride
  * 8 or 16, entries index_words apart at d_index, as gcow_encode_device writes them; or GCOW_INDEX_PACKED16, entries
  * as gcow_index_pack16_device writes them -- the size of the 16-block index, decoded in 8-block chunks).
+ * Every slot may hold anything from its stream's last bit to stream_words, and so may the 2 words after the last
+ * slot (the decoders' contract above: gcow_decode_device). stream_words may be odd: streams then start 8 bytes off a
+ * 16-byte boundary, which the kernels allow for. Index entries are relative to each stream's first word. The output
+ * follows the same rules as gcow_decode_device's (any stride, any element-aligned base).
  */
 gcow_status gcow_decode_mean_device(const zfp_input* field, const gcow_params* p, const uint64_t* d_streams,
                                     size_t streams_bytes, uint64_t stream_words, uint32_t nstreams,
@@ -681,7 +707,20 @@ size_t gcow_encode_zfp_workspace_bytes(const zfp_input* field, const gcow_params
 gcow_status gcow_encode_device_zfp(const zfp_input* field, const gcow_params* p, void* d_out, size_t out_capacity,
                                    uint64_t* d_total_bits, void* d_workspace, size_t workspace_bytes,
                                    void* hip_stream);
-/* Decode a stream whose first block starts at bit_offset (e.g. gcow_read_header()'s return value). */
+/*
+ * Decode a stream whose first block starts at bit_offset (e.g. gcow_read_header()'s return value); any bit_offset,
+ * with anything below it. The contract of gcow_decode_device holds (in_bytes counts from d_in, not from the offset).
+ *   - Index entries are RELATIVE TO bit_offset: block c * index_stride starts at bit bit_offset + d_index[c]. An
+ *     index written by gcow_encode_device for the headerless stream serves the same stream behind a header unchanged.
+ *   - Random access to a part of a field: a part cut along the slowest axis at a multiple of 4 rows consists of
+ *     whole blocks that are consecutive in the stream (1-D: any multiple of 4 values). Describe the part alone in
+ *     `field` and enter the whole stream at its first block b: fixed rate at bit_offset = b * maxbits; variable rate
+ *     with d_index advanced to the part's first entry, d_index + b / index_stride (b a multiple of index_stride), and
+ *     the bit_offset the entries are relative to -- 0 for the absolute entries gcow_encode_device and
+ *     gcow_encode_device_append write. d_in and in_bytes stay those of the whole stream.
+ *   - Whole-word fixed-rate streams (1-D rate 8 and 16, 3-D blocks of 2^k words) take their word kernels when
+ *     bit_offset is a multiple of 32 and the generic block decoder otherwise; the values are the same.
+ */
 gcow_status gcow_decode_device_at(const zfp_input* field, const gcow_params* p, const void* d_in, size_t in_bytes,
                                   uint64_t bit_offset, const uint64_t* d_index, uint32_t index_stride,
                                   void* hip_stream);

@@ -114,15 +114,23 @@ def _mean_op(orc, mode):
     return orc.rate(v[0], 1) if len(v) == 1 else orc.expert(*v)
 
 
-@pytest.mark.parametrize("mode", list(MEAN_MODES))
-@pytest.mark.parametrize("world", [1, 2, 3, 8])
-@pytest.mark.parametrize("stride", [16, 8, "packed"])
+def _mean_fixed(mode):
+    v = MEAN_MODES[mode]
+    return isinstance(v, tuple) and (len(v) == 1 or v[0] == v[1])
+
+
+def _mean_strides(mode):
+    """The index forms a mode runs with: fixed rate takes no index, so it runs once (under the id of stride 16)."""
+    return [16] if _mean_fixed(mode) else [16, 8, "packed"]
+
+
+@pytest.mark.parametrize("stride,world,mode", [(s, w, m) for s in [16, 8, "packed"] for w in [1, 2, 3, 8]
+                                               for m in MEAN_MODES if s in _mean_strides(m)])
 def test_decode_mean_vs_oracle(gc, orc, mode, world, stride):
     n = 4 * 20001 + 2  # a partial last block; > 128 index chunks; 5001 blocks: the last 16-block entry has no midpoint
     op = _mean_op(orc, mode)
     fixed = op.minbits == op.maxbits
-    if fixed and stride != 16:
-        pytest.skip("fixed rate takes no index")
+    assert fixed == _mean_fixed(mode)
     buckets = [_bucket(orc, n, 900 + r, mode.startswith("bf16")) for r in range(world)]
     encs = [gc.encode(_dev(b), _P(gc, op), index_stride=0 if fixed else _enc_stride(stride)) for b in buckets]
     lens = [e.bits for e in encs]
@@ -145,10 +153,9 @@ def _bf16_rne(a: np.ndarray) -> np.ndarray:
     return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
 
 
-@pytest.mark.parametrize("mode", list(MEAN_MODES))
-@pytest.mark.parametrize("world", [1, 3])
-@pytest.mark.parametrize("layout", ["contiguous", "strided"])
-@pytest.mark.parametrize("stride", [16, 8, "packed"])
+@pytest.mark.parametrize("stride,layout,world,mode",
+                         [(s, lay, w, m) for s in [16, 8, "packed"] for lay in ["contiguous", "strided"]
+                          for w in [1, 3] for m in MEAN_MODES if s in _mean_strides(m)])
 def test_decode_mean_bf16_output(gc, orc, mode, world, layout, stride):
     """decode_mean into a bf16 bucket (the hook's receive side for bf16 gradients): the fp32 mean of the oracle
     decodes, rounded to nearest even, written in place -- contiguous (8-byte block stores, the lean kernels' transposed
@@ -156,8 +163,7 @@ def test_decode_mean_bf16_output(gc, orc, mode, world, layout, stride):
     n = 4 * 20001 + 2
     op = _mean_op(orc, mode)
     fixed = op.minbits == op.maxbits
-    if fixed and stride != 16:
-        pytest.skip("fixed rate takes no index")
+    assert fixed == _mean_fixed(mode)
     buckets = [_bucket(orc, n, 700 + r, mode.startswith("bf16")) for r in range(world)]
     encs = [gc.encode(_dev(b), _P(gc, op), index_stride=0 if fixed else _enc_stride(stride)) for b in buckets]
     sw = max((e.bits + 63) // 64 for e in encs) + (0 if fixed else 1)
