@@ -7,7 +7,8 @@ memory, streams and torch.distributed (RCCL).
 from ._ffi import GcowError, GcowParams, load  # noqa: F401
 
 __all__ = ["GcowError", "GcowParams", "load", "codec", "dist", "TensorListRoundtrip", "roundtrip_tensors",
-           "roundtrip_gradients", "TensorListRelative", "roundtrip_tensors_relative", "roundtrip_gradients_relative"]
+           "roundtrip_gradients", "TensorListRelative", "roundtrip_tensors_relative", "roundtrip_gradients_relative",
+           "TensorListFitted", "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted"]
 
 
 def __getattr__(name):
@@ -16,7 +17,8 @@ def __getattr__(name):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("TensorListRoundtrip", "roundtrip_tensors", "roundtrip_gradients", "TensorListRelative",
-                "roundtrip_tensors_relative", "roundtrip_gradients_relative"):
+                "roundtrip_tensors_relative", "roundtrip_gradients_relative", "TensorListFitted",
+                "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted"):
         import importlib
         return getattr(importlib.import_module(".codec", __name__), name)
     raise AttributeError(name)

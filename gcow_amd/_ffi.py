@@ -137,6 +137,9 @@ def load():
         "gcow_encode_fitted_device": (i32, [pi, u32, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
         "gcow_roundtrip_fitted_device": (i32, [pi, u32, vp, vp, i32, vp, vp]),
         "gcow_rate_table_residual_device": (i32, [pi, vp, u32, vp, vp, sz, vp]),
+        "gcow_rate_table_list_workspace_bytes": (sz, [vp, sz]),
+        "gcow_rate_table_list_device": (i32, [vp, vp, sz, u32, vp, vp, sz, vp]),
+        "gcow_roundtrip_list_fitted_device": (i32, [vp, vp, sz, u32, vp, vp, vp]),
         "gcow_encode_residual_fitted_device": (i32, [pi, u32, vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),

@@ -265,13 +265,17 @@ class TensorListRoundtrip:
 
     def __init__(self, params: GcowParams):
         self.L = load()
-        self.params = params
+        self._p = params    # the plan's parameter set (`params` below; a subclass may give that name another meaning)
         self.rebuilds = 0
         self._key = None
         self._h = None      # pinned int64 host plan
         self._d = None      # its device copy
         self._used = 0
         self._uploaded = None  # event after the last upload: the host plan is not rewritten before it
+
+    @property
+    def params(self) -> GcowParams:
+        return self._p
 
     @staticmethod
     def _dt(t):
@@ -316,7 +320,7 @@ class TensorListRoundtrip:
             self._h = torch.empty(words, dtype=torch.int64).pin_memory()
             self._d = torch.empty(words, dtype=torch.int64, device=dev)
         used = C.c_size_t(0)
-        check(self.L.gcow_roundtrip_list_plan(ins, ous, cnt, n, in_dt, out_dt, C.byref(self.params),
+        check(self.L.gcow_roundtrip_list_plan(ins, ous, cnt, n, in_dt, out_dt, C.byref(self._p),
                                               self._h.data_ptr(), self._h.numel() * 8, C.byref(used)),
               "gcow_roundtrip_list_plan")
         self._used = int(used.value)
@@ -337,7 +341,8 @@ class TensorListRoundtrip:
               "gcow_roundtrip_list_plan_stats")
         return s
 
-    def __call__(self, tensors, outs=None, bits: torch.Tensor | None = None, stream=None):
+    def _prepare(self, tensors, outs, bits, stream):
+        """The checks of a call and the plan made current for it -> (tensors, outs, device, stream)."""
         tensors = list(tensors)
         outs = list(outs) if outs is not None else None
         dev = self._check(tensors, outs)
@@ -354,8 +359,12 @@ class TensorListRoundtrip:
             self._key = None
             self._plan(tensors, outs, in_dt, out_dt, dev, stream)
             self._key = key
+        return tensors, outs, dev, stream
+
+    def __call__(self, tensors, outs=None, bits: torch.Tensor | None = None, stream=None):
+        tensors, outs, dev, stream = self._prepare(tensors, outs, bits, stream)
         check(self.L.gcow_roundtrip_list_device(self._h.data_ptr(), self._d.data_ptr(), self._used,
-                                                C.byref(self.params),
+                                                C.byref(self._p),
                                                 bits.data_ptr() if bits is not None else None, stream.cuda_stream),
               "gcow_roundtrip_list_device")
         return outs if outs is not None else tensors
@@ -872,6 +881,130 @@ def roundtrip_fitted(x: torch.Tensor, fit, maxprec: int = 64, out: torch.Tensor 
                                              bits.data_ptr() if bits is not None else None, _stream_ptr(stream))
     check(st, "gcow_roundtrip_fitted_device")
     return out
+
+
+# ------------------------------------------------------------------------------------------- bit budget, tensor list
+RATE_TABLE_LIST_MAX_GRID = 1024  # workgroups of the table pass over a plan (csrc/kernels.h kRateTableListMaxGrid)
+
+
+class TensorListFitted(TensorListRoundtrip):
+    """Accuracy mode under a bit budget over a tensor list, with no host read: the rate table of the concatenation
+    (gcow_rate_table_list_device), the device fit against floor(bits_per_value * N) bits and the fitted round trip
+    (gcow_roundtrip_list_fitted_device), every tensor read and written where it lies. Each tensor receives its slice
+    of codec.roundtrip_fitted(torch.cat(...), bits_per_value, maxprec), bit for bit. A TensorListRoundtrip planned for
+    a set without a block budget: the plan, the table, the workspace, the gcow_fit record and a bit count are
+    allocated once (on the first call: the device is the tensors'), so later calls allocate nothing, synchronise
+    nothing and capture into a graph that then follows the data it is replayed on. N is known on the host from the
+    tensors. `table` and `fit` are the device tensors of the last call, `bits` its int64[1] bit count; `params()`
+    reads the record."""
+
+    def __init__(self, bits_per_value: float, maxprec: int = 64):
+        super().__init__(fitted_params(maxprec, 0))  # the plan reads neither maxprec nor minexp
+        self.bits_per_value, self.maxprec = float(bits_per_value), int(maxprec)
+        self.budget = 0
+        self.table = self.fit = self.ws = self.bits = None
+        self.ws_bytes = 0
+
+    def _buffers(self, dev):
+        if self.table is None or self.table.device != dev:
+            self.ws_bytes = self.L.gcow_rate_table_list_workspace_bytes(self._h.data_ptr(), self._used)
+            self.ws = torch.empty(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+            self.table = torch.empty(RATE_TABLE_ENTRIES, dtype=torch.int64, device=dev)
+            self.fit = new_fit_record(dev)
+            self.bits = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _table(self, stream):
+        check(self.L.gcow_rate_table_list_device(self._h.data_ptr(), self._d.data_ptr(), self._used, self.maxprec,
+                                                 self.table.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                                 stream.cuda_stream), "gcow_rate_table_list_device")
+
+    def rate_table(self, tensors, stream=None) -> torch.Tensor:
+        """The int64[288] device table of the concatenation (codec.rate_table(torch.cat(...), maxprec), exactly). The
+        pass reads inputs only: a plan already made for these tensors, with whatever outputs, is used as it is."""
+        tensors = list(tensors)
+        dev = self._check(tensors, None)
+        k = self._key
+        same = k is not None and k[2] == dev and k[3] == tuple((t.data_ptr(), t.numel()) for t in tensors) and \
+            k[0] == (self._dt(tensors[0].dtype) if tensors else DTYPE_FLOAT)
+        if same:
+            stream = stream if stream is not None else torch.cuda.current_stream(dev)
+        else:
+            tensors, _, dev, stream = self._prepare(tensors, None, None, stream)
+        self._buffers(dev)
+        self._table(stream)
+        return self.table
+
+    def run(self, tensors, fit, outs=None, bits: torch.Tensor | None = None, stream=None):
+        """__call__ with the budget or the minexp word given per call: `fit` is a number (bits per value: table, fit
+        and round trip) or a minexp word / gcow_fit record on the tensors' device (the round trip alone)."""
+        tensors, outs, dev, stream = self._prepare(tensors, outs, bits, stream)
+        self._buffers(dev)
+        if isinstance(fit, torch.Tensor):
+            word = _minexp_ptr(fit, dev)
+        else:
+            self.budget = int(math.floor(fit * sum(t.numel() for t in tensors)))
+            self._table(stream)
+            fit_device(self.table, self.budget, self.fit, stream)
+            word = self.fit.data_ptr()
+        check(self.L.gcow_roundtrip_list_fitted_device(self._h.data_ptr(), self._d.data_ptr(), self._used,
+                                                       self.maxprec, word,
+                                                       (bits if bits is not None else self.bits).data_ptr(),
+                                                       stream.cuda_stream), "gcow_roundtrip_list_fitted_device")
+        return outs if outs is not None else tensors
+
+    def __call__(self, tensors, outs=None, bits: torch.Tensor | None = None, stream=None):
+        return self.run(tensors, self.bits_per_value, outs, bits, stream)
+
+    params = FittedEncoder.params
+
+
+def _list_fitted_plan(plan, bits_per_value, maxprec, what):
+    if plan is None:
+        return TensorListFitted(bits_per_value, maxprec)
+    if not isinstance(plan, TensorListFitted) or plan.maxprec != int(maxprec):
+        raise GcowError("%s: the plan object must be a TensorListFitted of maxprec %d" % (what, int(maxprec)))
+    return plan
+
+
+def rate_table_tensors(tensors, maxprec: int = 64, stream=None, plan: TensorListFitted | None = None) -> torch.Tensor:
+    """codec.rate_table of the concatenation of a list of tensors, each read where it lies
+    (gcow_rate_table_list_device): the int64[288] device tensor of stream lengths of cat(tensors) under
+    expert(1, 16658, maxprec, minexp), minexp = -154 .. 133, exactly. tensors as roundtrip_tensors'. plan: a
+    TensorListFitted of this maxprec kept by the caller (the table is its `table`); without it the call plans and
+    allocates every time."""
+    return _list_fitted_plan(plan, 0.0, maxprec, "rate_table_tensors").rate_table(tensors, stream)
+
+
+def roundtrip_tensors_fitted(tensors, fit, maxprec: int = 64, outs=None, bits: torch.Tensor | None = None, stream=None,
+                             plan: TensorListFitted | None = None):
+    """codec.roundtrip_fitted(torch.cat(tensors), fit, maxprec) written back tensor by tensor, without the
+    concatenation ever existing (gcow_roundtrip_list_fitted_device). `fit` is a number -- bits per value: the list's
+    rate table and its device fit against floor(fit * N) bits are launched first -- or a minexp word (an int32 device
+    tensor or a gcow_fit record). No host read either way. tensors / outs / bits as roundtrip_tensors'; plan: a
+    TensorListFitted of this maxprec kept by the caller. Returns the list of outputs."""
+    if not isinstance(fit, torch.Tensor) and not isinstance(fit, (int, float)):
+        raise GcowError("roundtrip_tensors_fitted: fit must be a number of bits per value or a device minexp word")
+    bpv = 0.0 if isinstance(fit, torch.Tensor) else fit
+    return _list_fitted_plan(plan, bpv, maxprec, "roundtrip_tensors_fitted").run(tensors, fit, outs, bits, stream)
+
+
+def roundtrip_gradients_fitted(parameters, bits_per_value: float, maxprec: int = 64, bits: torch.Tensor | None = None,
+                               stream=None, cache: dict | None = None) -> TensorListFitted:
+    """roundtrip_gradients in accuracy mode under a bit budget: p.grad of every parameter that has one, in iteration
+    order, round-tripped in place as one field of N values under the finest tolerance whose stream takes at most
+    floor(bits_per_value * N) bits -- table, fit and round trip on the device, no host read. The plan object lives in
+    `cache` (default: codec.gradient_plans) under ("fitted", bits_per_value, maxprec, device). Returns it (stats(),
+    rebuilds, table, fit, bits, params())."""
+    grads = [q.grad for q in parameters if q.grad is not None]
+    if cache is None:
+        cache = gradient_plans
+    dev = grads[0].device if grads else None
+    key = ("fitted", float(bits_per_value), int(maxprec), str(dev))
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = TensorListFitted(bits_per_value, maxprec)
+    plan(grads, None, bits, stream)
+    return plan
 
 
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):

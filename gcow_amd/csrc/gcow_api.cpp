@@ -1368,6 +1368,59 @@ gcow_status gcow_roundtrip_list_device(const void* h_plan, const void* d_plan, s
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- bit budget, tensor list
+// The plan of both calls: gcow_roundtrip_list_plan's, made for a set without a block budget. Its own maxprec / minexp
+// are not read.
+static gcow_status rtl_nobudget_header(const void* h_plan, size_t plan_bytes, gcow::RtListHeader& H)
+{
+  gcow_status st = rtl_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (H.domain != (uint32_t)gcow::kRoundtripVar)
+    return fail(GCOW_ERR_INVALID, "the plan was not made for a set without a block budget (minbits <= 1, maxbits >= 160)");
+  return GCOW_OK;
+}
+
+size_t gcow_rate_table_list_workspace_bytes(const void* h_plan, size_t plan_bytes)
+{
+  gcow::RtListHeader H;
+  if (rtl_header(h_plan, plan_bytes, H)) return 0;
+  return gcow::rate_table_workspace_bytes();  // the two 288-bin arrays, whatever the list
+}
+
+gcow_status gcow_rate_table_list_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                        uint64_t* d_table, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+  gcow::RtListHeader H;
+  gcow_status st = rtl_nobudget_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  if (!d_table || (uintptr_t)d_table % 8) return fail(GCOW_ERR_INVALID, "null or misaligned table");
+  if (!d_workspace || (uintptr_t)d_workspace % 8 || workspace_bytes < gcow::rate_table_workspace_bytes())
+    return fail(GCOW_ERR_INVALID, "workspace null, misaligned or smaller than gcow_rate_table_list_workspace_bytes()");
+  GCOW_HIP(gcow::launch_rate_table_list1d(H, d_plan, maxprec, d_table, (uint64_t*)d_workspace, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_list_fitted_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
+                                              uint32_t maxprec, const int32_t* d_minexp, uint64_t* d_total_bits,
+                                              void* hip_stream)
+{
+  gcow::RtListHeader H;
+  gcow_status st = rtl_nobudget_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+  if (!d_total_bits || (uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "null or misaligned d_total_bits");
+  GCOW_HIP(gcow::launch_set_u64(d_total_bits, 0, hip_stream));
+  if (H.nvals == 0) return GCOW_OK;
+  GCOW_HIP(gcow::launch_roundtrip_list1d_fitted(H, d_plan, maxprec, d_minexp, d_total_bits, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- round trip, relative
 static const size_t kRelHeaderBytes = (sizeof(gcow::RtRelHeader) + 15) / 16 * 16;
 

@@ -195,6 +195,19 @@ hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* t
 // stored; both rows 16-byte aligned take the wide loads, else every tile is gathered. ws and table as above.
 hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint32_t maxprec, uint64_t* table,
                                      uint64_t* ws, void* stream);
+// The two ends of every table pass (rate_table1d.hip): the workspace zeroed by a kernel, in stream order; the
+// workspace's two 288-bin arrays summed into the table of a field of nblocks blocks.
+hipError_t launch_rate_table_zero(uint64_t* ws, void* stream);
+hipError_t launch_rate_table_finish(const uint64_t* ws, uint64_t nblocks, uint64_t* table, void* stream);
+// The table of the concatenation X of a tensor list (rate_table_list1d.hip): what launch_rate_table1d writes for the
+// contiguous X of the plan's input dtype, read where the tensors lie through the plan of launch_roundtrip_list1d (any
+// domain's plan has the segment table; a plan of kRoundtripVar has direct chunks too). h: the plan's header (HOST
+// copy); d_plan: the whole plan on the DEVICE; only the input pointers are read. ws and table as above. One launch: a
+// workgroup takes items blockIdx.x, + grid, ... of the gather units (8 per gather chunk, 256 blocks each) followed by
+// the direct chunks, and the grid is min(items, kRateTableListMaxGrid).
+constexpr uint32_t kRateTableListMaxGrid = 1024;
+hipError_t launch_rate_table_list1d(const RtListHeader& h, const void* d_plan, uint32_t maxprec, uint64_t* table,
+                                    uint64_t* ws, void* stream);
 // The fit on the device (rate_table1d.hip k_rate_table_fit; include/gcow.h gcow_fit has this layout): the smallest t
 // with table[t] <= budget -> {kRateTableMinExpLo + t, 0, table[t]}; none -> {the last entry's minexp, 1, table[287]}.
 // One workgroup of kRateTableEntries lanes; the record is written with plain stores and nothing past it.
@@ -226,6 +239,10 @@ hipError_t launch_encode_resid1d_var_fitted(const void* x, int x_dtype, uint64_t
 hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nvals, uint32_t maxprec,
                                      const int32_t* d_minexp, bool rows16, void* out, int out_dtype, uint64_t* total,
                                      void* stream);
+// launch_roundtrip_list1d under that set, for a plan of kRoundtripVar (roundtrip_list1d.hip keeps _fitted twins of its
+// two no-budget kernels). total: required, zeroed by the caller.
+hipError_t launch_roundtrip_list1d_fitted(const RtListHeader& h, const void* d_plan, uint32_t maxprec,
+                                          const int32_t* d_minexp, uint64_t* total, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

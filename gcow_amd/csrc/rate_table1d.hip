@@ -30,6 +30,9 @@
 //                         node's fill wrote a stale 16-byte pattern from the second replay on (the workspace then held
 //                         that pattern plus the pass's own counts, and the table was garbage).
 // The table is written whole. Integer adds only: the result does not depend on the order of the atomics.
+// The per-block pieces (RtRaw, rt_add, rt_block, rt_values, rt_tile, the LDS arrays' zeroing and flush) are in
+// rate_table1d.h, which the pass over a tensor list's plan shares (rate_table_list1d.hip; it runs between this unit's
+// zero and finish kernels through launch_rate_table_zero / launch_rate_table_finish).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,133 +42,26 @@
 #include "field_io.h"
 #include "kernels.h"
 #include "lean1d.h"
+#include "rate_table1d.h"
 #include "var1d_prep.h"
 
 namespace gcow {
 
 namespace {
 
-constexpr uint32_t RTT = 256;                    // lanes per workgroup
-constexpr uint32_t RTU = 4;                      // consecutive blocks per lane
-constexpr uint32_t RT_TILE = RTT * RTU;          // blocks per workgroup and iteration
-constexpr uint32_t RT_BINS = kRateTableEntries;  // 288
-constexpr uint32_t RT_COPIES = 16;               // interleaved LDS copies of each array
-constexpr uint32_t RT_MAXGRID = 1024;            // 4 workgroups of 36 KB LDS per CU on 256 CUs
-static_assert(RT_TILE * 4 == kRateTableTileValues, "kernels.h states the tile for the tests");
+constexpr uint32_t RT_MAXGRID = 1024;  // 4 workgroups of 36 KB LDS per CU on 256 CUs
 // A 32-bit LDS bin cannot wrap: a block adds at most 12 to one bin (L(1) - 1 <= 12; a step start or end is at most 4
 // in magnitude), a call has fewer than 2^32 blocks in at most 2^22 tiles, so a workgroup of a full grid sees at most
 // 2^22 / RT_MAXGRID + 1 tiles = 2^22 + 2^10 blocks, and (2^22 + 2^10) * 12 < 2^26.
 static_assert(((1ull << 32) / RT_TILE / RT_MAXGRID + 1) * RT_TILE * 12 < (1ull << 31), "LDS bins are 32-bit");
 
-// the lane's RTU consecutive blocks of a tile as raw words (fp32: one 16-byte load per block; bf16: one per two)
-template <int DT>
-struct RtRaw {
-  static constexpr int N = DT == DT_BF16 ? RTU / 2 : RTU;
-  uint4 w[N];
-  // a tile of whole blocks in a contiguous, 16-byte aligned field
-  __device__ __forceinline__ void load_wide(const FieldDesc& F, uint32_t t)
-  {
-    const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
-    const uint4* src = (const uint4*)F.data + (DT == DT_BF16 ? bl / 2 : bl);
-#pragma unroll
-    for (int h = 0; h < N; h++) w[h] = src[h];
-  }
-  // any tile: blocks past the field read nothing, the partial last block is padded as the encoder pads it
-  __device__ __forceinline__ void gather(const FieldDesc& F, uint32_t t)
-  {
-    const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
-    uint32_t* d = (uint32_t*)w;
-#pragma unroll
-    for (uint32_t k = 0; k < RTU; k++) {
-      float f[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (bl + k < F.nblocks) gather_block<1, DT>(F, (uint32_t)(bl + k), f);
-      if constexpr (DT == DT_BF16) {
-        d[2 * k] = (__float_as_uint(f[0]) >> 16) | (__float_as_uint(f[1]) & 0xffff0000u);
-        d[2 * k + 1] = (__float_as_uint(f[2]) >> 16) | (__float_as_uint(f[3]) & 0xffff0000u);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) d[4 * k + i] = __float_as_uint(f[i]);
-      }
-    }
-  }
-  __device__ __forceinline__ void block(uint32_t k, float* f) const
-  {
-    const uint32_t* d = (const uint32_t*)w;
-    if constexpr (DT == DT_BF16) {
-      f[0] = __uint_as_float(d[2 * k] << 16);
-      f[1] = __uint_as_float(d[2 * k] & 0xffff0000u);
-      f[2] = __uint_as_float(d[2 * k + 1] << 16);
-      f[3] = __uint_as_float(d[2 * k + 1] & 0xffff0000u);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; i++) f[i] = __uint_as_float(d[4 * k + i]);
-    }
-  }
-};
-
-// bin t of the lane's copy; t outside the table (only -1 occurs) is dropped
-__device__ __forceinline__ void rt_add(uint32_t* h, uint32_t copy, int t, uint32_t v)
-{
-  if ((uint32_t)t < RT_BINS) atomicAdd(h + (uint32_t)t * RT_COPIES + copy, v);
-}
-
-// one block's updates; a1 = a - 1 = emax + 157, the entry at which the block has precision 1
-__device__ __forceinline__ void rt_block(uint32_t* step, uint32_t* imp, uint32_t copy, int a1, const uint32_t* u,
-                                         uint32_t pmax)
-{
-  const uint32_t S2 = u[2] | u[3], S1 = u[1] | S2, S0 = u[0] | S1;
-  const uint32_t z[3] = {min(ffbh_hw(S0), 32u), min(ffbh_hw(S1), 32u), min(ffbh_hw(S2), 32u)};
-  uint32_t l1 = 12u, start = 1u, level = 0u;  // l1 = L(1) - 1
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const uint32_t b = shl_hw(u[j], z[j]) >> 31;  // bit 31 - z_j of u_j; z_j = 32: u_j = 0
-    l1 += z[j] == 0 ? b : 0u;
-    l1 -= min(z[j], 1u);
-    start += z[j] <= 1u ? 1u : 0u;
-    const bool in = z[j] >= 1u && z[j] < pmax;
-    if (in && b) rt_add(imp, copy, a1 - (int)z[j], 1u);
-    if (in && z[j] >= 2u) {
-      rt_add(step, copy, a1 - (int)z[j], 1u);
-      level++;
-    }
-  }
-  rt_add(imp, copy, a1, l1);
-  rt_add(step, copy, a1 - 1, start);
-  rt_add(step, copy, a1 - (int)pmax, 0u - (start + level));
-}
-
-template <int DT>
-__device__ __forceinline__ void rt_tile(const FieldDesc& F, const RtRaw<DT>& raw, uint32_t t, uint32_t pmax,
-                                        uint32_t* step, uint32_t* imp, uint32_t copy)
-{
-  const uint64_t bl = (uint64_t)t * RT_TILE + (uint64_t)threadIdx.x * RTU;
-#pragma unroll
-  for (uint32_t k = 0; k < RTU; k++) {
-    float f[4];
-    raw.block(k, f);
-    uint32_t u[4];
-    bool inf;
-    const uint32_t m = v1_coeffs(f, u, inf);
-    int a1 = (int)(m >> 23) + 31;  // emax = E - 126
-    bool live = m != 0u;
-    if (inf) {  // Inf / NaN: the generic rule for the exponent and the cast (emax from the finite values, Inf: 0)
-      const Params full{1u, 16658u, 64u, -1074};  // precision > 0 for every emax: be = emax + 127, 0 for a zero block
-      const BlockHead h = prepare_block<1>(f, full, u);
-      a1 = (int)h.be + 30;
-      live = h.be != 0u;
-    }
-    if (live && bl + k < F.nblocks) rt_block(step, imp, copy, a1, u, pmax);
-  }
-}
-
 template <int DT>
 __global__ __launch_bounds__(RTT) void k_rate_table1d(FieldDesc F, uint32_t pmax, uint32_t ntiles,
                                                       unsigned long long* __restrict__ ws)
 {
-  __shared__ uint32_t hist[2 * RT_BINS * RT_COPIES];
+  __shared__ uint32_t hist[RT_HIST_WORDS];
   const uint32_t tid = threadIdx.x;
-  for (uint32_t i = tid; i < 2 * RT_BINS * RT_COPIES; i += RTT) hist[i] = 0u;
-  __syncthreads();
+  rt_hist_zero(hist);
   uint32_t* step = hist;
   uint32_t* imp = hist + RT_BINS * RT_COPIES;
   const uint32_t copy = tid & (RT_COPIES - 1u);
@@ -182,12 +78,7 @@ __global__ __launch_bounds__(RTT) void k_rate_table1d(FieldDesc F, uint32_t pmax
     cur = nxt;
   }
   __syncthreads();
-  for (uint32_t i = tid; i < 2 * RT_BINS; i += RTT) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < RT_COPIES; c++) s += hist[i * RT_COPIES + c];
-    if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
-  }
+  rt_hist_flush(hist, ws);
 }
 
 // The lane's RTU blocks of y = x + e from its x words and e words: the single fadd of the residual encoder
@@ -214,10 +105,9 @@ template <int DT>
 __global__ __launch_bounds__(RTT) void k_rate_table1d_xe(FieldDesc F, const float* __restrict__ e_in, uint32_t pmax,
                                                          uint32_t ntiles, unsigned long long* __restrict__ ws)
 {
-  __shared__ uint32_t hist[2 * RT_BINS * RT_COPIES];
+  __shared__ uint32_t hist[RT_HIST_WORDS];
   const uint32_t tid = threadIdx.x;
-  for (uint32_t i = tid; i < 2 * RT_BINS * RT_COPIES; i += RTT) hist[i] = 0u;
-  __syncthreads();
+  rt_hist_zero(hist);
   uint32_t* step = hist;
   uint32_t* imp = hist + RT_BINS * RT_COPIES;
   const uint32_t copy = tid & (RT_COPIES - 1u);
@@ -251,12 +141,7 @@ __global__ __launch_bounds__(RTT) void k_rate_table1d_xe(FieldDesc F, const floa
     cure = nxte;
   }
   __syncthreads();
-  for (uint32_t i = tid; i < 2 * RT_BINS; i += RTT) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < RT_COPIES; c++) s += hist[i * RT_COPIES + c];
-    if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
-  }
+  rt_hist_flush(hist, ws);
 }
 
 __global__ __launch_bounds__(RT_BINS) void k_rate_table_zero(unsigned long long* __restrict__ ws)
@@ -315,14 +200,25 @@ hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, Ra
 
 size_t rate_table_workspace_bytes() { return 2 * RT_BINS * sizeof(uint64_t); }
 
+hipError_t launch_rate_table_zero(uint64_t* ws, void* stream)
+{
+  k_rate_table_zero<<<1, RT_BINS, 0, (hipStream_t)stream>>>((unsigned long long*)ws);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_table_finish(const uint64_t* ws, uint64_t nblocks, uint64_t* table, void* stream)
+{
+  k_rate_table_finish<<<1, RT_BINS, 0, (hipStream_t)stream>>>((const unsigned long long*)ws, nblocks, table);
+  return hipGetLastError();
+}
+
 // zero -> pass -> finish; e_in null: the table of x (y = x + 0 codes as x), else of y = x + e
 hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint32_t maxprec, uint64_t* table,
                                      uint64_t* ws, void* stream)
 {
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* w = (unsigned long long*)ws;
-  k_rate_table_zero<<<1, RT_BINS, 0, st>>>(w);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_rate_table_zero(ws, stream);
   if (e != hipSuccess) return e;
   const uint32_t pmax = std::min(maxprec, 32u);
   if (F.nblocks && pmax) {
@@ -335,8 +231,7 @@ hipError_t launch_rate_table1d_resid(const FieldDesc& F, const float* e_in, uint
     else k_rate_table1d_xe<DT_F32><<<grid, RTT, 0, st>>>(F, e_in, pmax, ntiles, w);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  k_rate_table_finish<<<1, RT_BINS, 0, st>>>(w, F.nblocks, table);
-  return hipGetLastError();
+  return launch_rate_table_finish(ws, F.nblocks, table, stream);
 }
 
 hipError_t launch_rate_table1d(const FieldDesc& F, uint32_t maxprec, uint64_t* table, uint64_t* ws, void* stream)

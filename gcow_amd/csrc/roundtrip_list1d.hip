@@ -11,6 +11,8 @@
 //                            block; every chunk of the generic domain): one workgroup per RtListGather, each lane U
 //                            blocks, every value located in the segment table and loaded on its own, the block coded
 //                            by the domain's block function (rt_fixed_code, rt_var_code, rt_block_generic)
+//   k_roundtrip_list_var_fitted, k_roundtrip_list_gather_fitted   the no-budget kernels with minexp from a word of
+//                            device memory (gcow_roundtrip_list_fitted_device)
 // The results are bit for bit those of gcow_roundtrip_device on the contiguous X.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +22,7 @@
 
 #include "field_io.h"
 #include "roundtrip1d.h"
+#include "rtlist_gather.h"
 
 namespace gcow {
 
@@ -166,7 +169,78 @@ __global__ __launch_bounds__(256) void k_roundtrip_list_gather(const RtListGathe
   if (total) rt_count(lsum, cnt_sh, total);  // total: a kernel argument, uniform over the workgroup
 }
 
+// ---------------------------------------------------------------------------------------------- minexp from the device
+// gcow_roundtrip_list_fitted_device (include/gcow.h): the two no-budget kernels under
+// Params{1, 16658, maxprec, clamp(*d_minexp)}, the word read when the kernel runs (fitted_params_dev, var1d_prep.h).
+// Twins with their own argument lists, as in roundtrip1d.hip, so that the host-parameter kernels above keep their
+// code. The bit count is always taken. In the direct kernel the word is read and waited for ahead of rt_var_chunk's
+// first asm row load (fitted_params_dev<true>), and the descriptor's words are scalar loads the compiler waits for
+// itself: the rule of rt_var_block (N = U - 1 for every block) holds as it stands. The gather kernel has no
+// hand-counted wait; its blocks are located by rtl_gather_block (rtlist_gather.h), the text of the loop above.
+template <int DT_IN, int DT_OUT, int U>
+__global__ __launch_bounds__(256) void k_roundtrip_list_var_fitted(const RtListDirect* __restrict__ desc,
+                                                                   uint32_t maxprec,
+                                                                   const int32_t* __restrict__ d_minexp,
+                                                                   uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  const Params p = fitted_params_dev<true>(maxprec, d_minexp);
+  pipe_v4i rin;
+  __amdgpu_buffer_rsrc_t rout;
+  uint32_t nb;
+  rtl_resources<DT_IN, DT_OUT>(desc, rin, rout, nb);
+  const uint32_t lsum = rt_var_chunk<DT_IN, DT_OUT, true, U>(rin, rout, threadIdx.x, nb, p);
+  rt_count(lsum, cnt_sh, total);
+}
+
+template <int DT_IN, int DT_OUT, int U>
+__global__ __launch_bounds__(256) void k_roundtrip_list_gather_fitted(const RtListGather* __restrict__ chunks,
+                                                                      const RtListSeg* __restrict__ segs,
+                                                                      uint64_t nvals, uint32_t maxprec,
+                                                                      const int32_t* __restrict__ d_minexp,
+                                                                      uint64_t* total)
+{
+  __shared__ uint32_t cnt_sh[4];
+  const Params p = fitted_params_dev<false>(maxprec, d_minexp);
+  constexpr uint32_t OE = DT_OUT == DT_BF16 ? 2u : 4u;
+  const RtListGather c = chunks[blockIdx.x];
+  const uint64_t nblocks = (nvals + 3) / 4;
+  const uint32_t nb = (uint32_t)min<uint64_t>(kRtListChunkBlocks, nblocks - c.b0);
+  uint32_t lsum = 0;
+#pragma unroll 1
+  for (int k = 0; k < U; k++) {
+    const uint32_t i = threadIdx.x + 256u * k;
+    const bool act = i < nb;
+    float f[4] = {0.f, 0.f, 0.f, 0.f}, d[4];
+    char* o[4] = {nullptr, nullptr, nullptr, nullptr};
+    const uint32_t nv = rtl_gather_block<DT_IN, OE>(c, segs, nvals, i, act, f, o);  // all read before any is written
+    const uint32_t len = rt_var_code(f, p, d);  // lanes past the chunk code a zero block
+    lsum += act ? len : 0u;
+#pragma unroll
+    for (uint32_t x = 0; x < 4u; x++)
+      if (x < nv) {
+        if constexpr (DT_OUT == DT_BF16) *(uint16_t*)o[x] = (uint16_t)bf16_rne(d[x]);
+        else *(float*)o[x] = d[x];
+      }
+  }
+  rt_count(lsum, cnt_sh, total);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
+template <int DT_IN, int DT_OUT>
+static void launch_rtl_fitted_t(const RtListHeader& h, const char* d_plan, uint32_t maxprec, const int32_t* d_minexp,
+                                uint64_t* total, hipStream_t st)
+{
+  constexpr int U = GCOW_RT_U;
+  const RtListDirect* dd = (const RtListDirect*)(d_plan + h.off_direct);
+  const RtListGather* gg = (const RtListGather*)(d_plan + h.off_gather);
+  const RtListSeg* ss = (const RtListSeg*)(d_plan + h.off_segs);
+  if (h.ndirect) k_roundtrip_list_var_fitted<DT_IN, DT_OUT, U><<<h.ndirect, 256, 0, st>>>(dd, maxprec, d_minexp, total);
+  if (h.ngather)
+    k_roundtrip_list_gather_fitted<DT_IN, DT_OUT, U><<<h.ngather, 256, 0, st>>>(gg, ss, h.nvals, maxprec, d_minexp,
+                                                                               total);
+}
+
 template <int DT_IN, int DT_OUT>
 static void launch_rtl_t(const RtListHeader& h, const char* d_plan, const Params& p, uint64_t* total, hipStream_t st)
 {
@@ -208,6 +282,22 @@ hipError_t launch_roundtrip_list1d(const RtListHeader& h, const void* d_plan, co
   } else {
     if (h.out_dtype == DT_F32) launch_rtl_t<DT_BF16, DT_F32>(h, dp, p, total, st);
     else launch_rtl_t<DT_BF16, DT_BF16>(h, dp, p, total, st);
+  }
+  return hipGetLastError();
+}
+
+// h.domain == kRoundtripVar (the caller has checked it): the plan's direct chunks are the no-budget kernel's
+hipError_t launch_roundtrip_list1d_fitted(const RtListHeader& h, const void* d_plan, uint32_t maxprec,
+                                          const int32_t* d_minexp, uint64_t* total, void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  const char* dp = (const char*)d_plan;
+  if (h.in_dtype == DT_F32) {
+    if (h.out_dtype == DT_F32) launch_rtl_fitted_t<DT_F32, DT_F32>(h, dp, maxprec, d_minexp, total, st);
+    else launch_rtl_fitted_t<DT_F32, DT_BF16>(h, dp, maxprec, d_minexp, total, st);
+  } else {
+    if (h.out_dtype == DT_F32) launch_rtl_fitted_t<DT_BF16, DT_F32>(h, dp, maxprec, d_minexp, total, st);
+    else launch_rtl_fitted_t<DT_BF16, DT_BF16>(h, dp, maxprec, d_minexp, total, st);
   }
   return hipGetLastError();
 }

@@ -554,6 +554,44 @@ gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxpre
                                          data_type out_dtype, uint64_t* d_total_bits, void* hip_stream);
 
 /*
+ * Accuracy mode under a bit budget over a tensor list: the rate table and the fitted round trip of the concatenation
+ * X = cat(t_0 ... t_{S-1}) (N values, as in gcow_roundtrip_list_device's contract), every tensor read and written
+ * where it lies. Table, gcow_rate_table_fit_device and round trip go on one stream with no host read, and can be
+ * captured into one graph. The budget is one for the whole list (one table for the concatenation); a table per tensor
+ * is not offered.
+ *
+ * The plan. Both calls take a plan of gcow_roundtrip_list_plan as it is (h_plan, d_plan, plan_bytes as
+ * gcow_roundtrip_list_device's), made for any set WITHOUT A BLOCK BUDGET: minbits <= 1 and maxbits >= 160
+ * (gcow_roundtrip_list_stats.domain == 1), e.g. {1, 16658, maxprec, 0}. The plan's own maxprec and minexp are not
+ * read: maxprec is an argument here and minexp is the table's index or the device word. A plan of another domain
+ * returns GCOW_ERR_INVALID. (gcow_roundtrip_list_device still wants exactly the plan's parameter set.)
+ *
+ * gcow_rate_table_list_workspace_bytes: the workspace of the table call for that plan (0 for a NULL, short or foreign
+ *   plan; else positive, and the same for every list).
+ * gcow_rate_table_list_device: d_table[t], t = 0 .. 287 (DEVICE uint64), is exactly what gcow_rate_table_device writes
+ *   for the contiguous X of the plan's input dtype, i.e. the *d_total_bits of gcow_roundtrip_list_device under
+ *   {1, 16658, maxprec, -154 + t}. Only the plan's input pointers are read. The table is written whole and nothing
+ *   past it; neither the table nor the workspace (8-byte aligned) needs zeroing by the caller, and the workspace is
+ *   zeroed by a kernel in stream order, not by a memset node. No allocation and no synchronisation; legal inside a
+ *   stream capture. N = 0 gives an all-zero table. Integer sums only: the same bits run to run.
+ * gcow_roundtrip_list_fitted_device: with m = clamp(*d_minexp, -154, 133), the word read ON THE DEVICE when the kernels
+ *   run, every out_s and *d_total_bits (DEVICE uint64, required) are bit for bit what gcow_roundtrip_list_device writes
+ *   under {1, 16658, maxprec, m} -- hence what gcow_roundtrip_fitted_device writes for the contiguous X. Dtypes and
+ *   outputs are the plan's; in place (out_s == in_s) is allowed for equal dtypes, as in the list call. N = 0 writes
+ *   *d_total_bits = 0. d_minexp: any 4-byte aligned DEVICE word, unchanged by the call; the first word of a gcow_fit
+ *   is the intended source. Asynchronous on hip_stream, no allocation, no synchronisation.
+ * GCOW_ERR_INVALID, all decided on the host before any launch: a NULL, short (plan_bytes) or foreign h_plan; a plan of
+ * another domain; a NULL or misaligned (8 bytes) d_plan, d_table, d_workspace or d_total_bits; a NULL or misaligned
+ * (4 bytes) d_minexp; a workspace below the query; maxprec as check_params has it for {1, 16658, maxprec, 0}.
+ */
+size_t gcow_rate_table_list_workspace_bytes(const void* h_plan, size_t plan_bytes);
+gcow_status gcow_rate_table_list_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                        uint64_t* d_table, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+gcow_status gcow_roundtrip_list_fitted_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
+                                              uint32_t maxprec, const int32_t* d_minexp, uint64_t* d_total_bits,
+                                              void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by

@@ -25,7 +25,13 @@ usage: roundtrip_time.py --list [--only NAME]
 --relative: the tolerance relative to each tensor (codec.roundtrip_tensors_relative -> gcow_roundtrip_rel_device,
 rel_bits 8) next to roundtrip_tensors at accuracy 1e-3, in place on the same ResNet-50-shaped list, fp32 and bf16
 (relative_leg's docstring).
-usage: roundtrip_time.py --relative [--only NAME]"""
+usage: roundtrip_time.py --relative [--only NAME]
+
+--fitted-list: accuracy mode under a bit budget over the same ResNet-50-shaped fp32 list (fitted_list_leg's docstring):
+the composed flow torch.cat + rate table + device fit + roundtrip_fitted + one copy_ per tensor against
+codec.TensorListFitted, at 8.0 and 2.5 bits per value, with the table pass, the fit and the round trip of both broken
+out. Medians over interleaved rounds with their spread.
+usage: roundtrip_time.py --fitted-list [--only NAME] [--rounds 9]"""
 import json
 import math
 import os
@@ -226,8 +232,144 @@ def relative_leg():
         del ta, tr
 
 
+def fitted_list_leg():
+    """Form A is the flow the parent offers for a tensor list under a bit budget: torch.cat into a preallocated flat
+    buffer, the rate table of it (a kept codec.RateTable), codec.fit_device into a kept record, codec.roundtrip_fitted
+    in place on the flat buffer under the record, one copy_ per tensor into the outputs. Form B is a kept
+    codec.TensorListFitted called with the same tensors and outputs. Nothing is allocated in either timed call and
+    neither reads anything on the host. The inputs are never written (outputs are tensors of their own), so every
+    launch of a form does the same work. Checked first: the outputs, the bit count, the table and the fit record of
+    the two forms are identical. Then every part -- A, B, and of each its table pass, its fit and its round trip, and
+    A's cat and copy-back, and both forms captured into a graph and replayed (which leaves the host out: an eager call
+    of either form is bound by its launches and by Python) -- is timed in rounds that take the parts in turn in one
+    process: 3 untimed and 20 timed launches per part and round, mean HIP-event time; reported are the median over the
+    rounds and [min, max].
+    table_within_spread: the two table passes' [min, max] overlap. list_faster: B's maximum is below A's minimum."""
+    rounds = arg("--rounds", 9)
+    shapes = resnet50_shapes()
+    total = sum(math.prod(s) for s in shapes)
+    src = torch.empty(total, dtype=torch.float32, device="cuda")
+    codec.fill_normal(src, 1e-3, seed=0x67636F77, inject=True)
+    offs = [0]
+    for s in shapes:
+        offs.append(offs[-1] + math.prod(s))
+    ts = [src[offs[i]:offs[i + 1]].clone().view(s) for i, s in enumerate(shapes)]
+    views = [t.view(-1) for t in ts]
+    outs_a = [torch.empty_like(t) for t in ts]
+    outs_b = [torch.empty_like(t) for t in ts]
+    flat = torch.empty(total, dtype=torch.float32, device="cuda")
+    backs = [flat[offs[i]:offs[i + 1]].view(s) for i, s in enumerate(shapes)]
+    for bpv in (8.0, 2.5):
+        name = "fitted_list_resnet50_fp32_%gbpv" % bpv
+        if only and name != only:
+            continue
+        budget = int(math.floor(bpv * total))
+        table_a = codec.RateTable(total, torch.float32)
+        fit_a = codec.new_fit_record()
+        bits_a = torch.zeros(1, dtype=torch.int64, device="cuda")
+        bits_b = torch.zeros(1, dtype=torch.int64, device="cuda")
+        plan = codec.TensorListFitted(bpv)
+
+        def a_cat():
+            torch.cat(views, out=flat)
+
+        cur = {"st": st}  # the stream the forms launch on: the timing stream, or the capturing one
+
+        def a_table():
+            table_a(flat, 64, cur["st"])
+
+        def a_fit():
+            codec.fit_device(table_a.table, budget, fit_a, cur["st"])
+
+        def a_rt():
+            codec.roundtrip_fitted(flat, fit_a, 64, out=flat, bits=bits_a, stream=cur["st"])
+
+        def a_back():
+            for o, b in zip(outs_a, backs):
+                o.copy_(b)
+
+        def a_fn():
+            a_cat()
+            a_table()
+            a_fit()
+            a_rt()
+            a_back()
+
+        def b_fn():
+            plan(ts, outs_b, bits_b, cur["st"])
+
+        # B's parts go to the C ABI with the plan as b_fn left it: through the object each would pay again for the
+        # comparison of 161 pointers with the plan's key, which b_fn pays once
+        def b_table():
+            plan._table(st)
+
+        def b_fit():
+            codec.fit_device(plan.table, budget, plan.fit, st)
+
+        def b_rt():
+            plan.L.gcow_roundtrip_list_fitted_device(plan._h.data_ptr(), plan._d.data_ptr(), plan._used, 64,
+                                                     plan.fit.data_ptr(), bits_b.data_ptr(), st.cuda_stream)
+
+        def captured(fn):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                cur["st"] = torch.cuda.current_stream()
+                fn()
+            cur["st"] = st
+            return g.replay
+
+        a_fn()
+        b_fn()
+        torch.cuda.synchronize()
+        same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs_a, outs_b))
+        same = same and int(bits_a.item()) == int(bits_b.item()) and torch.equal(table_a.table, plan.table)
+        same = same and codec.read_fit(fit_a) == codec.read_fit(plan.fit)
+        stats = plan.stats()
+        me, status, fbits = codec.read_fit(plan.fit)
+        res = {"config": name, "tensors": len(shapes), "n": total, "bits_per_value": bpv, "same_result": bool(same),
+               "fitted_minexp": me, "fit_status": status, "stream_bits_per_value": round(fbits / total, 3),
+               "direct_chunks": int(stats.direct_chunks), "gather_chunks": int(stats.gather_chunks), "rounds": rounds}
+        # a_rt alone runs on whatever a_cat left in flat: the round trip of a round trip, the same work per launch
+        a_graph, b_graph = captured(a_fn), captured(b_fn)
+        a_graph()
+        b_graph()
+        torch.cuda.synchronize()
+        same = same and all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs_a, outs_b))
+        res["same_result"] = bool(same)
+        parts = [("composed", a_fn), ("list", b_fn), ("composed_graph", a_graph), ("list_graph", b_graph),
+                 ("composed_cat", a_cat), ("composed_table", a_table),
+                 ("list_table", b_table), ("composed_fit", a_fit), ("list_fit", b_fit), ("composed_roundtrip", a_rt),
+                 ("list_roundtrip", b_rt), ("composed_copy_back", a_back)]
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.25:
+            a_fn()
+            b_fn()
+            torch.cuda.synchronize()
+        got = {k: [] for k, _ in parts}
+        for _ in range(rounds):
+            for k, fn in parts:
+                if k == "composed_roundtrip":
+                    a_cat()  # the flat buffer holds the inputs again
+                got[k].append(timed(fn, 3, 20))
+        for k, v in got.items():
+            v.sort()
+            res[k + "_ms"] = {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+        res["composed_over_list"] = round(res["composed_ms"]["median"] / res["list_ms"]["median"], 3)
+        res["list_faster"] = bool(res["list_ms"]["max"] < res["composed_ms"]["min"])
+        res["composed_over_list_graph"] = round(res["composed_graph_ms"]["median"] / res["list_graph_ms"]["median"], 3)
+        res["list_graph_faster"] = bool(res["list_graph_ms"]["max"] < res["composed_graph_ms"]["min"])
+        res["table_list_over_composed"] = round(res["list_table_ms"]["median"] / res["composed_table_ms"]["median"], 3)
+        res["table_within_spread"] = bool(res["list_table_ms"]["min"] <= res["composed_table_ms"]["max"]
+                                          and res["composed_table_ms"]["min"] <= res["list_table_ms"]["max"])
+        res["plan_rebuilds"] = plan.rebuilds
+        print(json.dumps(res), flush=True)
+
+
 if "--list" in sys.argv:
     list_leg()
+    sys.exit(0)
+if "--fitted-list" in sys.argv:
+    fitted_list_leg()
     sys.exit(0)
 if "--relative" in sys.argv:
     relative_leg()
