@@ -8,7 +8,9 @@ from ._ffi import GcowError, GcowParams, load  # noqa: F401
 
 __all__ = ["GcowError", "GcowParams", "load", "codec", "dist", "TensorListRoundtrip", "roundtrip_tensors",
            "roundtrip_gradients", "TensorListRelative", "roundtrip_tensors_relative", "roundtrip_gradients_relative",
-           "TensorListFitted", "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted"]
+           "TensorListFitted", "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted",
+           "TensorListFittedPerTensor", "rate_tables_tensors", "fit_device_batch",
+           "roundtrip_tensors_fitted_per_tensor", "roundtrip_gradients_fitted_per_tensor"]
 
 
 def __getattr__(name):
@@ -18,7 +20,9 @@ def __getattr__(name):
         return importlib.import_module("." + name, __name__)
     if name in ("TensorListRoundtrip", "roundtrip_tensors", "roundtrip_gradients", "TensorListRelative",
                 "roundtrip_tensors_relative", "roundtrip_gradients_relative", "TensorListFitted",
-                "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted"):
+                "rate_table_tensors", "roundtrip_tensors_fitted", "roundtrip_gradients_fitted",
+                "TensorListFittedPerTensor", "rate_tables_tensors", "fit_device_batch",
+                "roundtrip_tensors_fitted_per_tensor", "roundtrip_gradients_fitted_per_tensor"):
         import importlib
         return getattr(importlib.import_module(".codec", __name__), name)
     raise AttributeError(name)

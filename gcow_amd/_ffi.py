@@ -140,6 +140,10 @@ def load():
         "gcow_rate_table_list_workspace_bytes": (sz, [vp, sz]),
         "gcow_rate_table_list_device": (i32, [vp, vp, sz, u32, vp, vp, sz, vp]),
         "gcow_roundtrip_list_fitted_device": (i32, [vp, vp, sz, u32, vp, vp, vp]),
+        "gcow_rate_table_rel_workspace_bytes": (sz, [vp, sz]),
+        "gcow_rate_table_rel_device": (i32, [vp, vp, sz, u32, vp, vp, sz, vp]),
+        "gcow_rate_table_fit_batch_device": (i32, [vp, sz, vp, i32, vp, vp]),
+        "gcow_roundtrip_rel_fitted_device": (i32, [vp, vp, sz, u32, vp, u32, vp, vp]),
         "gcow_encode_residual_fitted_device": (i32, [pi, u32, vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),

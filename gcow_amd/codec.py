@@ -1007,6 +1007,214 @@ def roundtrip_gradients_fitted(parameters, bits_per_value: float, maxprec: int =
     return plan
 
 
+# ------------------------------------------------------------------------------------- bit budget, a tensor at a time
+MINEXP_FLOOR = -94  # the default floor of a per-tensor fit: gcow_roundtrip_rel_device's, for the same reason
+
+
+def _fit_records(fits: torch.Tensor, n: int, dev, what: str):
+    """-> (pointer, stride in 4-byte words) of per-tensor minexp words: int64[n, 2] gcow_fit records (stride 4) or
+    int32[n] packed words (stride 1)."""
+    if not (isinstance(fits, torch.Tensor) and fits.is_cuda and fits.device == dev and fits.is_contiguous()):
+        raise GcowError("%s: fits must be a contiguous tensor on the tensors' device" % what)
+    if fits.dtype == torch.int64 and fits.numel() == FIT_WORDS * n:
+        return fits.data_ptr(), 4
+    if fits.dtype == torch.int32 and fits.numel() == n:
+        return fits.data_ptr(), 1
+    raise GcowError("%s: fits must be int64[%d, 2] gcow_fit records or int32[%d] minexp words" % (what, n, n))
+
+
+def fit_device_batch(tables: torch.Tensor, budgets: torch.Tensor, minexp_floor: int = RATE_TABLE_MINEXP_LO,
+                     out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """gcow_rate_table_fit_batch_device: table s (tables: int64[S, 288] on the device) fitted against budgets[s]
+    (int64[S] on the device, in bits) over the entries at minexp >= minexp_floor, one workgroup per table and no host
+    read. -> `out` (default: new), int64[S, 2]: S gcow_fit records -- row s is what fit_device(tables[s], budgets[s])
+    writes when the floor is -154; where no entry fits, (133, status 1, tables[s][287])."""
+    if not (isinstance(tables, torch.Tensor) and tables.is_cuda and tables.dtype == torch.int64 and tables.dim() == 2
+            and tables.shape[1] == RATE_TABLE_ENTRIES and tables.is_contiguous()):
+        raise GcowError("fit_device_batch: tables must be a contiguous int64[S, %d] device tensor" % RATE_TABLE_ENTRIES)
+    n = tables.shape[0]
+    if not (isinstance(budgets, torch.Tensor) and budgets.is_cuda and budgets.device == tables.device
+            and budgets.dtype == torch.int64 and budgets.numel() == n and budgets.is_contiguous()):
+        raise GcowError("fit_device_batch: budgets must be a contiguous int64[%d] tensor on the tables' device" % n)
+    if out is None:
+        out = torch.zeros((n, FIT_WORDS), dtype=torch.int64, device=tables.device)
+    if not (out.is_cuda and out.device == tables.device and out.dtype == torch.int64 and out.numel() == FIT_WORDS * n
+            and out.is_contiguous()):
+        raise GcowError("fit_device_batch: out must be a contiguous int64[%d, %d] tensor on the tables' device"
+                        % (n, FIT_WORDS))
+    check(load().gcow_rate_table_fit_batch_device(tables.data_ptr() if n else None, n,
+                                                  budgets.data_ptr() if n else None, int(minexp_floor),
+                                                  out.data_ptr() if n else None, _stream_ptr(stream)),
+          "gcow_rate_table_fit_batch_device")
+    return out
+
+
+class TensorListFittedPerTensor(TensorListRelative):
+    """Accuracy mode under a bit budget for every tensor of a list, with no host read: tensor s is a field of its own
+    (as in TensorListRelative, whose plan this is), with its own rate table (gcow_rate_table_rel_device), its own
+    budget of floor(bits_per_value * n_s) bits, its own device fit over minexp >= minexp_floor
+    (gcow_rate_table_fit_batch_device) and the round trip under that fit (gcow_roundtrip_rel_fitted_device): tensor s
+    receives codec.roundtrip_fitted(t_s, fits[s], maxprec), bit for bit. The loud tensors of a gradient list neither
+    decide the quiet ones' tolerance nor take their bits, and the bits of each tensor are bounded.
+
+    The object owns the pinned plan and its device copy, the tables (`tables`, int64[S, 288]), the workspace, the
+    gcow_fit records (`fits`, int64[S, 2]: word 0 = minexp | status << 32, word 1 = bits), the device budgets
+    (`budgets`, int64[S]) and a bit count (`bits`, int64[1]). They are (re)made and the budgets uploaded only when the
+    plan is rebuilt -- pointers, counts, dtypes or device changed -- so later calls allocate nothing, synchronise
+    nothing and capture into one graph (a linear chain) that then follows the data it is replayed on. `rebuilds` and
+    `stats()` are TensorListRelative's. The default floor of -94 keeps blocks of scale below 2^-98 at precision 0
+    (they decode to +0, not to garbage: include/gcow.h); the relative form's cap for maxima in the top binade has no
+    counterpart here."""
+
+    def __init__(self, bits_per_value: float, maxprec: int = 64, minexp_floor: int = MINEXP_FLOOR):
+        super().__init__(0, maxprec)
+        self.bits_per_value, self.minexp_floor = float(bits_per_value), int(minexp_floor)
+        self.tables = self.fits = self.budgets = self.ws = self.bits = None
+        self.ws_bytes = 0
+        self._h_budgets = None
+
+    def _plan(self, tensors, outs, in_dt, out_dt, dev, stream):
+        if self._uploaded is not None:
+            self._uploaded.synchronize()  # the pinned budgets are still the source of a copy in flight
+        super()._plan(tensors, outs, in_dt, out_dt, dev, stream)
+        n = len(tensors)
+        if self.tables is None or self.tables.shape[0] != n or self.tables.device != dev:
+            self.ws_bytes = self.L.gcow_rate_table_rel_workspace_bytes(self._h.data_ptr(), self._used)
+            self.ws = torch.empty(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=dev)
+            self.tables = torch.empty((n, RATE_TABLE_ENTRIES), dtype=torch.int64, device=dev)
+            self.fits = torch.zeros((n, FIT_WORDS), dtype=torch.int64, device=dev)
+            self.budgets = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.bits = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._h_budgets = torch.zeros(n, dtype=torch.int64).pin_memory()
+        for s, t in enumerate(tensors):
+            self._h_budgets[s] = int(math.floor(self.bits_per_value * t.numel()))
+        with torch.cuda.stream(stream):
+            self.budgets.copy_(self._h_budgets, non_blocking=True)
+            self._uploaded = torch.cuda.Event()
+            self._uploaded.record(stream)
+
+    def _current(self, tensors, outs, bits, stream, what):
+        tensors = list(tensors)
+        outs = list(outs) if outs is not None else None
+        dev = self._check(tensors, outs)
+        if bits is not None and not (bits.is_cuda and bits.device == dev and bits.dtype == torch.int64
+                                     and bits.numel() == 1):
+            raise GcowError("%s: bits must be a one-element int64 tensor on the tensors' device" % what)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        in_dt = self._dt(tensors[0].dtype) if tensors else DTYPE_FLOAT
+        out_dt = self._dt(outs[0].dtype) if outs else in_dt
+        key = (in_dt, out_dt, dev, tuple((t.data_ptr(), t.numel()) for t in tensors),
+               tuple(o.data_ptr() for o in outs) if outs is not None else None)
+        if key != self._key:
+            self._key = None
+            self._plan(tensors, outs, in_dt, out_dt, dev, stream)
+            self._key = key
+        return tensors, outs, dev, stream
+
+    def _tables(self, n, stream):
+        check(self.L.gcow_rate_table_rel_device(self._h.data_ptr(), self._d.data_ptr(), self._used, self.maxprec,
+                                                self.tables.data_ptr() if n else None,
+                                                self.ws.data_ptr(), self.ws_bytes, stream.cuda_stream),
+              "gcow_rate_table_rel_device")
+
+    def rate_tables(self, tensors, stream=None) -> torch.Tensor:
+        """The int64[S, 288] device tables: row s is codec.rate_table(t_s, maxprec), exactly (zeros for an empty
+        tensor). The pass reads inputs only: a plan already made for these tensors, with whatever outputs, is used as
+        it is."""
+        tensors = list(tensors)
+        dev = self._check(tensors, None)
+        k = self._key
+        same = k is not None and k[2] == dev and k[3] == tuple((t.data_ptr(), t.numel()) for t in tensors) and \
+            k[0] == (self._dt(tensors[0].dtype) if tensors else DTYPE_FLOAT)
+        if same:
+            stream = stream if stream is not None else torch.cuda.current_stream(dev)
+        else:
+            tensors, _, dev, stream = self._current(tensors, None, None, stream, "rate_tables_tensors")
+        self._tables(len(tensors), stream)
+        return self.tables
+
+    def run(self, tensors, fits=None, outs=None, bits: torch.Tensor | None = None, stream=None):
+        """__call__ with the fits given per call: None -- tables, fits against the object's budgets, round trip -- or
+        per-tensor minexp words on the tensors' device (int64[S, 2] gcow_fit records or int32[S] packed words: the
+        round trip alone). Words outside [-154, 133] are clamped."""
+        tensors, outs, dev, stream = self._current(tensors, outs, bits, stream, "roundtrip_tensors_fitted_per_tensor")
+        n = len(tensors)
+        if fits is None:
+            self._tables(n, stream)
+            fit_device_batch(self.tables, self.budgets, self.minexp_floor, self.fits, stream)
+            fits = self.fits
+        ptr, stride = _fit_records(fits, n, dev, "roundtrip_tensors_fitted_per_tensor")
+        check(self.L.gcow_roundtrip_rel_fitted_device(self._h.data_ptr(), self._d.data_ptr(), self._used,
+                                                      self.maxprec, ptr if n else None, stride,
+                                                      (bits if bits is not None else self.bits).data_ptr(),
+                                                      stream.cuda_stream), "gcow_roundtrip_rel_fitted_device")
+        return outs if outs is not None else tensors
+
+    def __call__(self, tensors, outs=None, bits: torch.Tensor | None = None, stream=None):
+        return self.run(tensors, None, outs, bits, stream)
+
+
+def _per_tensor_plan(plan, bits_per_value, maxprec, minexp_floor, what):
+    if plan is None:
+        return TensorListFittedPerTensor(bits_per_value, maxprec, minexp_floor)
+    if not isinstance(plan, TensorListFittedPerTensor) or plan.maxprec != int(maxprec):
+        raise GcowError("%s: the plan object must be a TensorListFittedPerTensor of maxprec %d" % (what, int(maxprec)))
+    return plan
+
+
+def rate_tables_tensors(tensors, maxprec: int = 64, stream=None,
+                        plan: TensorListFittedPerTensor | None = None) -> torch.Tensor:
+    """codec.rate_table of every tensor of a list from one pass, each read where it lies (gcow_rate_table_rel_device):
+    the int64[S, 288] device tensor whose row s holds the stream lengths of t_s under
+    expert(1, 16658, maxprec, minexp), minexp = -154 .. 133, exactly. tensors as roundtrip_tensors'. plan: a
+    TensorListFittedPerTensor of this maxprec kept by the caller (the tables are its `tables`); without it the call
+    plans and allocates every time."""
+    return _per_tensor_plan(plan, 0.0, maxprec, MINEXP_FLOOR, "rate_tables_tensors").rate_tables(tensors, stream)
+
+
+def roundtrip_tensors_fitted_per_tensor(tensors, fit, maxprec: int = 64, outs=None, bits: torch.Tensor | None = None,
+                                        stream=None, plan: TensorListFittedPerTensor | None = None,
+                                        minexp_floor: int = MINEXP_FLOOR):
+    """Every tensor round-tripped where it lies under its own fitted tolerance (gcow_roundtrip_rel_fitted_device).
+    `fit` is a number -- bits per value: every tensor's rate table and its device fit against floor(fit * n_s) bits
+    over minexp >= minexp_floor are launched first -- or per-tensor minexp words on the device (int64[S, 2] gcow_fit
+    records or int32[S]). Tensor s receives codec.roundtrip_fitted(t_s, word_s, maxprec) bit for bit; no host read
+    either way. tensors / outs / bits as roundtrip_tensors' (bits: the sum of the per-tensor stream lengths). plan: a
+    TensorListFittedPerTensor of this maxprec kept by the caller (a number must then be the plan's own
+    bits_per_value, and the floor the plan's). Returns the list of outputs."""
+    what = "roundtrip_tensors_fitted_per_tensor"
+    if isinstance(fit, torch.Tensor):
+        return _per_tensor_plan(plan, 0.0, maxprec, minexp_floor, what).run(tensors, fit, outs, bits, stream)
+    if not isinstance(fit, (int, float)):
+        raise GcowError("%s: fit must be a number of bits per value or device minexp words" % what)
+    p = _per_tensor_plan(plan, fit, maxprec, minexp_floor, what)
+    if (p.bits_per_value, p.minexp_floor) != (float(fit), int(minexp_floor)):
+        raise GcowError("%s: the plan object was made for %g bits per value and floor %d"
+                        % (what, p.bits_per_value, p.minexp_floor))
+    return p.run(tensors, None, outs, bits, stream)
+
+
+def roundtrip_gradients_fitted_per_tensor(parameters, bits_per_value: float, maxprec: int = 64,
+                                          bits: torch.Tensor | None = None, stream=None, cache: dict | None = None,
+                                          minexp_floor: int = MINEXP_FLOOR) -> TensorListFittedPerTensor:
+    """roundtrip_gradients under a bit budget per gradient tensor: p.grad of every parameter that has one, in
+    iteration order, round-tripped in place, each as a field of its own under the finest tolerance (minexp >=
+    minexp_floor) whose stream takes at most floor(bits_per_value * n_s) bits -- tables, fits and round trip on the
+    device, no host read. The plan object lives in `cache` (default: codec.gradient_plans) under ("fitted_per_tensor",
+    bits_per_value, maxprec, minexp_floor, device). Returns it (stats(), rebuilds, tables, fits, budgets, bits)."""
+    grads = [q.grad for q in parameters if q.grad is not None]
+    if cache is None:
+        cache = gradient_plans
+    dev = grads[0].device if grads else None
+    key = ("fitted_per_tensor", float(bits_per_value), int(maxprec), int(minexp_floor), str(dev))
+    plan = cache.get(key)
+    if plan is None:
+        plan = cache[key] = TensorListFittedPerTensor(bits_per_value, maxprec, minexp_floor)
+    plan(grads, None, bits, stream)
+    return plan
+
+
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):
     """OR src_bits bits of src into dst at dst_bit_offset (device words; dst zeroed beyond earlier content)."""
     L = load()

@@ -1598,6 +1598,65 @@ gcow_status gcow_roundtrip_rel_device(const void* h_plan, const void* d_plan, si
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- a budget per tensor
+size_t gcow_rate_table_rel_workspace_bytes(const void* h_plan, size_t plan_bytes)
+{
+  gcow::RtRelHeader H;
+  if (rel_header(h_plan, plan_bytes, H)) return 0;
+  return gcow::rate_table_rel_workspace_bytes(H.nsegs);  // a function of nsegs only
+}
+
+gcow_status gcow_rate_table_rel_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                       uint64_t* d_tables, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+  gcow::RtRelHeader H;
+  gcow_status st = rel_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!H.nsegs) return GCOW_OK;  // no tensor: no row
+  if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  if (!d_tables || (uintptr_t)d_tables % 8) return fail(GCOW_ERR_INVALID, "null or misaligned tables");
+  if (!d_workspace || (uintptr_t)d_workspace % 8 || workspace_bytes < gcow::rate_table_rel_workspace_bytes(H.nsegs))
+    return fail(GCOW_ERR_INVALID, "workspace null, misaligned or smaller than gcow_rate_table_rel_workspace_bytes()");
+  GCOW_HIP(gcow::launch_rate_table_rel1d(H, d_plan, maxprec, d_tables, (uint64_t*)d_workspace, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_rate_table_fit_batch_device(const uint64_t* d_tables, size_t ntables, const uint64_t* d_budgets,
+                                             int32_t minexp_floor, gcow_fit* d_fits, void* hip_stream)
+{
+  if (ntables >= (1ull << 31)) return fail(GCOW_ERR_UNSUPPORTED, "2^31 tables or more per call");
+  if (!ntables) return GCOW_OK;
+  if (!d_tables || (uintptr_t)d_tables % 8) return fail(GCOW_ERR_INVALID, "null or misaligned tables");
+  if (!d_budgets || (uintptr_t)d_budgets % 8) return fail(GCOW_ERR_INVALID, "null or misaligned budgets");
+  if (!d_fits || (uintptr_t)d_fits % 8) return fail(GCOW_ERR_INVALID, "null or misaligned fit records");
+  GCOW_HIP(gcow::launch_rate_table_fit_batch(d_tables, (uint32_t)ntables, d_budgets, minexp_floor,
+                                             (gcow::RateFit*)d_fits, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_roundtrip_rel_fitted_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
+                                             uint32_t maxprec, const int32_t* d_minexp, uint32_t minexp_stride_words,
+                                             uint64_t* d_total_bits, void* hip_stream)
+{
+  gcow::RtRelHeader H;
+  gcow_status st = rel_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!minexp_stride_words) return fail(GCOW_ERR_INVALID, "a stride of 0 words");
+  if ((uintptr_t)d_total_bits % 8) return fail(GCOW_ERR_INVALID, "misaligned d_total_bits");
+  if (H.nsegs) {
+    if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+    if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+  }
+  if (!H.nsegs && !d_total_bits) return GCOW_OK;  // an empty list and no bit count: nothing to write
+  GCOW_HIP(gcow::launch_roundtrip_rel1d_fitted(H, d_plan, maxprec, d_minexp, minexp_stride_words, d_total_bits,
+                                               hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

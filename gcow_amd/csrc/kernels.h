@@ -218,6 +218,25 @@ struct RateFit {
 };
 static_assert(sizeof(RateFit) == 16 && alignof(RateFit) == 8, "gcow_fit");
 hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, RateFit* fit, void* stream);
+// The same kernel, one workgroup per table: fits[s] from tables[s] (288 words each) against budgets[s] (DEVICE), over
+// the entries at minexp >= minexp_floor only (none fits: {133, 1, tables[s][287]}). minexp_floor = -154, ntables = 1:
+// launch_rate_table_fit with the budget in device memory.
+hipError_t launch_rate_table_fit_batch(const uint64_t* tables, uint32_t ntables, const uint64_t* budgets,
+                                       int32_t minexp_floor, RateFit* fits, void* stream);
+// A table per tensor of a list (rate_table_rel1d.hip): tables[s] (288 words, the caller's numbering, empty tensors
+// included: an all-zero row) is what launch_rate_table1d writes for tensor s as a field of its own, read through the
+// plan of launch_roundtrip_rel1d as it is (only the input pointers are read). ws: rate_table_rel_workspace_bytes(nsegs)
+// = kRateTableRelWords words per tensor (the two arrays and the tensor's block count, which the pass takes), zeroed by a
+// kernel in stream order. One launch over the plan: the gather chunks (one workgroup each), then the direct chunks cut
+// into min(ndirect, kRateTableRelMaxGrid) contiguous runs; then launch_rate_table_finish_batch, one workgroup per table
+// (table s from the words at ws + s * stride_words, its block count from word count_word of them).
+constexpr uint32_t kRateTableRelWords = 2 * kRateTableEntries + 1;
+constexpr uint32_t kRateTableRelMaxGrid = 1024;
+size_t rate_table_rel_workspace_bytes(uint32_t nsegs);
+hipError_t launch_rate_table_finish_batch(const uint64_t* ws, uint32_t ntables, uint64_t stride_words,
+                                          uint32_t count_word, uint64_t* tables, void* stream);
+hipError_t launch_rate_table_rel1d(const RtRelHeader& h, const void* d_plan, uint32_t maxprec, uint64_t* tables,
+                                   uint64_t* ws, void* stream);
 // Device-parameter ("fitted") forms: Params{1, 16658, maxprec, clamp(*d_minexp, -154, 133)} with the word read on the
 // device when the kernels run (fitted_params_dev, var1d_prep.h). Nothing on the host depends on minexp.
 // The tile-form kernels of var1d.hip are templates over their parameter source (ParamsHost / ParamsDev, var1d_prep.h):
@@ -243,6 +262,11 @@ hipError_t launch_roundtrip1d_fitted(const void* in, int in_dtype, uint64_t nval
 // two no-budget kernels). total: required, zeroed by the caller.
 hipError_t launch_roundtrip_list1d_fitted(const RtListHeader& h, const void* d_plan, uint32_t maxprec,
                                           const int32_t* d_minexp, uint64_t* total, void* stream);
+// launch_roundtrip_rel1d with tensor s under Params{1, 16658, maxprec, clamp(d_minexp[s * stride_words], -154, 133)},
+// the words read on the device (roundtrip_rel1d.hip: the same two kernels over another parameter source; no first
+// pass). total (optional): set to the sum of every block's bit length.
+hipError_t launch_roundtrip_rel1d_fitted(const RtRelHeader& h, const void* d_plan, uint32_t maxprec,
+                                         const int32_t* d_minexp, uint32_t stride_words, uint64_t* total, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

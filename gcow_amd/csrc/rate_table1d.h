@@ -1,7 +1,8 @@
 // rate_table1d.h -- the per-block pieces of the rate table, shared by the pass over a contiguous field
-// (rate_table1d.hip) and the pass over a tensor list's plan (rate_table_list1d.hip): a lane's raw rows, one block's
-// updates of the two 288-bin LDS histograms, and the histograms' zeroing and flush. The header of rate_table1d.hip has
-// the derivation.
+// (rate_table1d.hip), the pass over a tensor list's plan (rate_table_list1d.hip) and the pass that keeps a table per
+// tensor (rate_table_rel1d.hip): a lane's raw rows, one block's updates of two 288-bin histograms (in LDS, or straight
+// in a table's workspace: the sinks), the LDS histograms' zeroing and flush, and the rows of a plan's direct chunk.
+// The header of rate_table1d.hip has the derivation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include "field_io.h"
 #include "kernels.h"
 #include "lean1d.h"
+#include "pipe.h"
 #include "var1d_prep.h"
 
 namespace gcow {
@@ -75,9 +77,31 @@ __device__ __forceinline__ void rt_add(uint32_t* h, uint32_t copy, int t, uint32
   if ((uint32_t)t < RT_BINS) atomicAdd(h + (uint32_t)t * RT_COPIES + copy, v);
 }
 
+// Where a block's updates go. RtLdsSink: the lane's copy of the workgroup's two LDS arrays (every pass over whole
+// tiles). RtGlobalSink: straight to a table's 2 x 288 workspace words by 64-bit atomics, steps sign-extended as
+// rt_hist_flush extends them -- for blocks whose neighbours in the workgroup belong to other tables (the gather blocks
+// of rate_table_rel1d.hip).
+struct RtLdsSink {
+  uint32_t* step;
+  uint32_t* imp;
+  uint32_t copy;
+  __device__ __forceinline__ void add_step(int t, uint32_t v) const { rt_add(step, copy, t, v); }
+  __device__ __forceinline__ void add_imp(int t, uint32_t v) const { rt_add(imp, copy, t, v); }
+};
+
+struct RtGlobalSink {
+  unsigned long long* ws;  // the table's workspace: steps, then impulses
+  __device__ __forceinline__ void add(unsigned long long* h, int t, uint32_t v) const
+  {
+    if ((uint32_t)t < RT_BINS) atomicAdd(h + (uint32_t)t, (unsigned long long)(long long)(int32_t)v);
+  }
+  __device__ __forceinline__ void add_step(int t, uint32_t v) const { add(ws, t, v); }
+  __device__ __forceinline__ void add_imp(int t, uint32_t v) const { add(ws + RT_BINS, t, v); }
+};
+
 // one block's updates; a1 = a - 1 = emax + 157, the entry at which the block has precision 1
-__device__ __forceinline__ void rt_block(uint32_t* step, uint32_t* imp, uint32_t copy, int a1, const uint32_t* u,
-                                         uint32_t pmax)
+template <class Sink>
+__device__ __forceinline__ void rt_block(const Sink& sink, int a1, const uint32_t* u, uint32_t pmax)
 {
   const uint32_t S2 = u[2] | u[3], S1 = u[1] | S2, S0 = u[0] | S1;
   const uint32_t z[3] = {min(ffbh_hw(S0), 32u), min(ffbh_hw(S1), 32u), min(ffbh_hw(S2), 32u)};
@@ -89,21 +113,21 @@ __device__ __forceinline__ void rt_block(uint32_t* step, uint32_t* imp, uint32_t
     l1 -= min(z[j], 1u);
     start += z[j] <= 1u ? 1u : 0u;
     const bool in = z[j] >= 1u && z[j] < pmax;
-    if (in && b) rt_add(imp, copy, a1 - (int)z[j], 1u);
+    if (in && b) sink.add_imp(a1 - (int)z[j], 1u);
     if (in && z[j] >= 2u) {
-      rt_add(step, copy, a1 - (int)z[j], 1u);
+      sink.add_step(a1 - (int)z[j], 1u);
       level++;
     }
   }
-  rt_add(imp, copy, a1, l1);
-  rt_add(step, copy, a1 - 1, start);
-  rt_add(step, copy, a1 - (int)pmax, 0u - (start + level));
+  sink.add_imp(a1, l1);
+  sink.add_step(a1 - 1, start);
+  sink.add_step(a1 - (int)pmax, 0u - (start + level));
 }
 
 // one block from its four values (padded by the caller): the coefficients, then rt_block. real: the block exists.
 // A zero block adds nothing whether it exists or not.
-__device__ __forceinline__ void rt_values(const float* f, bool real, uint32_t pmax, uint32_t* step, uint32_t* imp,
-                                          uint32_t copy)
+template <class Sink>
+__device__ __forceinline__ void rt_values(const float* f, bool real, uint32_t pmax, const Sink& sink)
 {
   uint32_t u[4];
   bool inf;
@@ -116,7 +140,13 @@ __device__ __forceinline__ void rt_values(const float* f, bool real, uint32_t pm
     a1 = (int)h.be + 30;
     live = h.be != 0u;
   }
-  if (live && real) rt_block(step, imp, copy, a1, u, pmax);
+  if (live && real) rt_block(sink, a1, u, pmax);
+}
+
+__device__ __forceinline__ void rt_values(const float* f, bool real, uint32_t pmax, uint32_t* step, uint32_t* imp,
+                                          uint32_t copy)
+{
+  rt_values(f, real, pmax, RtLdsSink{step, imp, copy});
 }
 
 template <int DT>
@@ -147,6 +177,90 @@ __device__ __forceinline__ void rt_hist_flush(const uint32_t* hist, unsigned lon
 #pragma unroll
     for (uint32_t c = 0; c < RT_COPIES; c++) s += hist[i * RT_COPIES + c];
     if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
+  }
+}
+
+// rt_hist_flush that leaves the arrays zeroed for the next table (a workgroup that goes on to another tensor): the
+// caller has a barrier before it, as for rt_hist_flush, and one after it before the next update
+__device__ __forceinline__ void rt_hist_flush_zero(uint32_t* hist, unsigned long long* __restrict__ ws)
+{
+  for (uint32_t i = threadIdx.x; i < 2 * RT_BINS; i += RTT) {
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < RT_COPIES; c++) {
+      s += hist[i * RT_COPIES + c];
+      hist[i * RT_COPIES + c] = 0u;
+    }
+    if (s) atomicAdd(ws + i, (unsigned long long)(long long)(int32_t)s);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- direct chunks of a plan
+// A direct chunk of a list plan (RtListDirect, RtRelDirect: in, out, nb and one more word) is up to 2048 whole blocks of
+// one tensor whose first row is 4-byte aligned. It is read through a buffer resource over its nb rows by raw buffer
+// loads, as two halves of RT_TILE blocks, each lane RTU consecutive rows (rate_table_list1d.hip has the reasons).
+constexpr uint32_t RTL_HALF = RT_TILE;  // blocks per half chunk: 256 lanes x RTU
+static_assert(kRtListChunkBlocks == 2 * RTL_HALF, "a direct chunk is two halves");
+
+template <int DT> constexpr uint32_t rtl_row_bytes() { return DT == DT_BF16 ? 8u : 16u; }
+
+__device__ __forceinline__ uint32_t rtl_sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// The input rows of direct chunk d as a buffer resource: num_records = the chunk's nb rows in bytes. d is uniform
+// (derived from blockIdx and kernel arguments); readfirstlane makes every word provably so.
+template <int DT, class Direct>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rtl_in_rows(const Direct* __restrict__ d)
+{
+  const uint64_t in = d->in;
+  const uint32_t lo = rtl_sgpr((uint32_t)in), hi = rtl_sgpr((uint32_t)(in >> 32));
+  const uint32_t nb = min(rtl_sgpr(d->nb), kRtListChunkBlocks);
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, (int)(nb * rtl_row_bytes<DT>()),
+                                           0x00020000);
+}
+
+// the lane's RTU consecutive rows of half h of a chunk, as raw words
+template <int DT>
+struct RtlRows {
+  static constexpr int W = DT == DT_BF16 ? 2 : 4;  // dwords per row
+  uint32_t d[RTU * W];
+  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rin, uint32_t h)
+  {
+    const uint32_t row = h * RTL_HALF + threadIdx.x * RTU;  // < 2048: offsets stay below 2^15
+#pragma unroll
+    for (uint32_t k = 0; k < RTU; k++) {
+      const int off = (int)((row + k) * rtl_row_bytes<DT>());
+      if constexpr (DT == DT_BF16) {
+        const pipe_v2u v = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, 0);
+        d[2 * k] = v.x, d[2 * k + 1] = v.y;
+      } else {
+        const pipe_v4u v = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0);
+        d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+      }
+    }
+  }
+  __device__ __forceinline__ void block(uint32_t k, float* f) const
+  {
+    if constexpr (DT == DT_BF16) {
+      f[0] = __uint_as_float(d[2 * k] << 16);
+      f[1] = __uint_as_float(d[2 * k] & 0xffff0000u);
+      f[2] = __uint_as_float(d[2 * k + 1] << 16);
+      f[3] = __uint_as_float(d[2 * k + 1] & 0xffff0000u);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++) f[i] = __uint_as_float(d[4 * k + i]);
+    }
+  }
+};
+
+template <int DT>
+__device__ __forceinline__ void rtl_half(const RtlRows<DT>& rows, uint32_t pmax, uint32_t* step, uint32_t* imp,
+                                         uint32_t copy)
+{
+#pragma unroll
+  for (uint32_t k = 0; k < RTU; k++) {
+    float f[4];
+    rows.block(k, f);
+    rt_values(f, true, pmax, step, imp, copy);  // a row past the chunk is a zero block
   }
 }
 

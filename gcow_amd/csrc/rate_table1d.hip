@@ -24,7 +24,9 @@
 //                         to the global workspace with 64-bit atomics (steps sign-extended).
 //   k_rate_table1d_xe     the same pass over two rows, x and a carried error e: the table of y = x + e formed in
 //                         registers (gcow_rate_table_residual_device).
-//   k_rate_table_finish   288 x 2 workspace words -> the table: both suffix sums in one backward sweep.
+//   k_rate_table_finish   288 x 2 workspace words -> the table: both suffix sums in one backward sweep. One workgroup
+//                         per table: a batch of tables (rate_table_rel1d.hip, a table per tensor) is one launch.
+//   k_rate_table_fit      a table and a budget -> the gcow_fit record; one workgroup per table as well.
 //   k_rate_table_zero     the workspace zeroed in stream order ahead of the first kernel. A kernel and not a memset:
 //                         in a captured graph that also holds the fit and the encoder (FittedEncoder), the memset
 //                         node's fill wrote a stale 16-byte pattern from the second replay on (the workspace then held
@@ -150,16 +152,21 @@ __global__ __launch_bounds__(RT_BINS) void k_rate_table_zero(unsigned long long*
   ws[RT_BINS + threadIdx.x] = 0ull;
 }
 
+// Table blockIdx.x of a batch: its workspace is stride words after the one before, its row RT_BINS words. count_word
+// != 0: the table's block count is that word of its workspace (the per-tensor pass counts it there), else nblocks.
 __global__ __launch_bounds__(RT_BINS) void k_rate_table_finish(const unsigned long long* __restrict__ ws,
-                                                               uint64_t nblocks, uint64_t* __restrict__ table)
+                                                               uint64_t stride, uint32_t count_word, uint64_t nblocks,
+                                                               uint64_t* __restrict__ table)
 {
   __shared__ uint64_t s[2 * RT_BINS];
   const uint32_t tid = threadIdx.x;
+  ws += (uint64_t)blockIdx.x * stride;
+  table += (uint64_t)blockIdx.x * RT_BINS;
   s[tid] = ws[tid];
   s[RT_BINS + tid] = ws[RT_BINS + tid];
   __syncthreads();
   if (tid == 0) {
-    uint64_t level = 0, acc = nblocks;
+    uint64_t level = 0, acc = count_word ? (uint64_t)ws[count_word] : nblocks;
     for (int t = (int)RT_BINS - 1; t >= 0; t--) {
       level += s[t];
       acc += level + s[RT_BINS + t];
@@ -170,18 +177,24 @@ __global__ __launch_bounds__(RT_BINS) void k_rate_table_finish(const unsigned lo
   table[tid] = s[tid];
 }
 
-// The fit (gcow_rate_table_fit_device): the table is non-increasing, so the entries within the budget are a suffix and
-// the answer is the smallest index among them -- a min over the lanes whose entry fits, one LDS atomic each. No entry
-// fits: the coarsest set, flagged.
-__global__ __launch_bounds__(RT_BINS) void k_rate_table_fit(const uint64_t* __restrict__ table, uint64_t budget,
-                                                            RateFit* __restrict__ fit)
+// The fit (gcow_rate_table_fit_device, gcow_rate_table_fit_batch_device): the table is non-increasing, so the entries
+// within the budget are a suffix and the answer is the smallest index among them -- a min over the lanes whose entry
+// fits, one LDS atomic each. No entry fits: the coarsest set, flagged. One workgroup per table: table blockIdx.x
+// against budgets[blockIdx.x] (budgets null: budget) into fit[blockIdx.x]; lanes below lo -- a floor on minexp -- take
+// no part.
+__global__ __launch_bounds__(RT_BINS) void k_rate_table_fit(const uint64_t* __restrict__ table,
+                                                            const uint64_t* __restrict__ budgets, uint64_t budget,
+                                                            uint32_t lo, RateFit* __restrict__ fit)
 {
   __shared__ uint32_t best;
   const uint32_t tid = threadIdx.x;
+  table += (uint64_t)blockIdx.x * RT_BINS;
+  fit += blockIdx.x;
+  if (budgets) budget = budgets[blockIdx.x];
   if (tid == 0) best = RT_BINS;
   __syncthreads();
   const uint64_t v = table[tid];
-  if (v <= budget) atomicMin(&best, tid);
+  if (v <= budget && tid >= lo) atomicMin(&best, tid);
   __syncthreads();
   if (tid == min(best, RT_BINS - 1u)) {  // the lane that holds the chosen entry
     fit->minexp = kRateTableMinExpLo + (int32_t)tid;
@@ -194,7 +207,17 @@ __global__ __launch_bounds__(RT_BINS) void k_rate_table_fit(const uint64_t* __re
 
 hipError_t launch_rate_table_fit(const uint64_t* table, uint64_t budget_bits, RateFit* fit, void* stream)
 {
-  k_rate_table_fit<<<1, RT_BINS, 0, (hipStream_t)stream>>>(table, budget_bits, fit);
+  k_rate_table_fit<<<1, RT_BINS, 0, (hipStream_t)stream>>>(table, nullptr, budget_bits, 0u, fit);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_table_fit_batch(const uint64_t* tables, uint32_t ntables, const uint64_t* budgets,
+                                       int32_t minexp_floor, RateFit* fits, void* stream)
+{
+  if (!ntables) return hipSuccess;
+  const int64_t lo = (int64_t)minexp_floor - kRateTableMinExpLo;  // above 287: no lane takes part, status 1
+  k_rate_table_fit<<<ntables, RT_BINS, 0, (hipStream_t)stream>>>(
+      tables, budgets, 0ull, (uint32_t)std::min<int64_t>(std::max<int64_t>(lo, 0), RT_BINS), fits);
   return hipGetLastError();
 }
 
@@ -208,7 +231,16 @@ hipError_t launch_rate_table_zero(uint64_t* ws, void* stream)
 
 hipError_t launch_rate_table_finish(const uint64_t* ws, uint64_t nblocks, uint64_t* table, void* stream)
 {
-  k_rate_table_finish<<<1, RT_BINS, 0, (hipStream_t)stream>>>((const unsigned long long*)ws, nblocks, table);
+  k_rate_table_finish<<<1, RT_BINS, 0, (hipStream_t)stream>>>((const unsigned long long*)ws, 0ull, 0u, nblocks, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_rate_table_finish_batch(const uint64_t* ws, uint32_t ntables, uint64_t stride_words,
+                                          uint32_t count_word, uint64_t* tables, void* stream)
+{
+  if (!ntables) return hipSuccess;
+  k_rate_table_finish<<<ntables, RT_BINS, 0, (hipStream_t)stream>>>((const unsigned long long*)ws, stride_words,
+                                                                    count_word, 0ull, tables);
   return hipGetLastError();
 }
 

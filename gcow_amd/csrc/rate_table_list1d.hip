@@ -40,9 +40,7 @@ namespace gcow {
 
 namespace {
 
-constexpr uint32_t RTL_HALF = RT_TILE;                           // blocks per half chunk: 256 lanes x RTU
 constexpr uint32_t RTL_GU = kRtListChunkBlocks / RTT;            // gather units (one block per lane) per chunk
-static_assert(kRtListChunkBlocks == 2 * RTL_HALF, "a direct chunk is two halves");
 // A 32-bit LDS bin cannot wrap: a block adds at most 12 to one bin (rate_table1d.hip). X has fewer than 2^32 blocks,
 // so the plan has at most 2^32 / 2048 = 2^21 chunks (every chunk but the last is 2048 blocks of X). A workgroup of a
 // full grid takes at most 2^21 / kRateTableListMaxGrid + 1 = 2049 direct chunks and, were every chunk a gather chunk,
@@ -51,68 +49,7 @@ static_assert(kRtListChunkBlocks == 2 * RTL_HALF, "a direct chunk is two halves"
 static_assert((((1ull << 32) / kRtListChunkBlocks / kRateTableListMaxGrid + 1) * kRtListChunkBlocks +
                ((1ull << 32) / RTT / kRateTableListMaxGrid + 1) * RTT) * 12 < (1ull << 31), "LDS bins are 32-bit");
 
-template <int DT> constexpr uint32_t rtl_row_bytes() { return DT == DT_BF16 ? 8u : 16u; }
-
-__device__ __forceinline__ uint32_t rtl_sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// The input rows of direct chunk d as a buffer resource: num_records = the chunk's nb rows in bytes. d is uniform
-// (derived from blockIdx and kernel arguments); readfirstlane makes every word provably so.
-template <int DT>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rtl_in_rows(const RtListDirect* __restrict__ d)
-{
-  const uint64_t in = d->in;
-  const uint32_t lo = rtl_sgpr((uint32_t)in), hi = rtl_sgpr((uint32_t)(in >> 32));
-  const uint32_t nb = min(rtl_sgpr(d->nb), kRtListChunkBlocks);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, (int)(nb * rtl_row_bytes<DT>()),
-                                           0x00020000);
-}
-
-// the lane's RTU consecutive rows of half h of a chunk, as raw words
-template <int DT>
-struct RtlRows {
-  static constexpr int W = DT == DT_BF16 ? 2 : 4;  // dwords per row
-  uint32_t d[RTU * W];
-  __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t rin, uint32_t h)
-  {
-    const uint32_t row = h * RTL_HALF + threadIdx.x * RTU;  // < 2048: offsets stay below 2^15
-#pragma unroll
-    for (uint32_t k = 0; k < RTU; k++) {
-      const int off = (int)((row + k) * rtl_row_bytes<DT>());
-      if constexpr (DT == DT_BF16) {
-        const pipe_v2u v = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, 0);
-        d[2 * k] = v.x, d[2 * k + 1] = v.y;
-      } else {
-        const pipe_v4u v = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, 0);
-        d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
-      }
-    }
-  }
-  __device__ __forceinline__ void block(uint32_t k, float* f) const
-  {
-    if constexpr (DT == DT_BF16) {
-      f[0] = __uint_as_float(d[2 * k] << 16);
-      f[1] = __uint_as_float(d[2 * k] & 0xffff0000u);
-      f[2] = __uint_as_float(d[2 * k + 1] << 16);
-      f[3] = __uint_as_float(d[2 * k + 1] & 0xffff0000u);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; i++) f[i] = __uint_as_float(d[4 * k + i]);
-    }
-  }
-};
-
-template <int DT>
-__device__ __forceinline__ void rtl_half(const RtlRows<DT>& rows, uint32_t pmax, uint32_t* step, uint32_t* imp,
-                                         uint32_t copy)
-{
-#pragma unroll
-  for (uint32_t k = 0; k < RTU; k++) {
-    float f[4];
-    rows.block(k, f);
-    rt_values(f, true, pmax, step, imp, copy);  // a row past the chunk is a zero block
-  }
-}
-
+// RtlRows, rtl_in_rows and rtl_half -- a direct chunk's rows -- are rate_table1d.h's, shared with rate_table_rel1d.hip.
 template <int DT>
 __global__ __launch_bounds__(RTT) void k_rate_table_list(const RtListDirect* __restrict__ direct, uint32_t ndirect,
                                                          const RtListGather* __restrict__ gather, uint32_t ngather,

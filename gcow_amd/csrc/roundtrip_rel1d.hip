@@ -18,6 +18,10 @@
 //                    (encode.c:41-60), reads all before it writes any and writes only real values. A block never
 //                    crosses a tensor. The block function is rt_var_code with the lane's own Params
 // The results are bit for bit those of gcow_roundtrip_device on each tensor under its parameter set.
+// The two round trip kernels are templates over the source of that set (RelFromAbsmax / RelFromWord below): the second
+// instance is gcow_roundtrip_rel_fitted_device, tensor s under clamp(d_minexp[s * stride], -154, 133) from device memory
+// (a budget per tensor: rate_table_rel1d.hip writes the tables, k_rate_table_fit the words). It has no
+// first pass: *total is zeroed by k_rel_init and the coders run.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,7 +29,9 @@
 #include <utility>
 
 #include "field_io.h"
+#include "rel_locate.h"
 #include "roundtrip1d.h"
+#include "var1d_prep.h"
 
 namespace gcow {
 
@@ -34,8 +40,6 @@ static_assert(kRtRelGatherBlocks <= kRtListChunkBlocks, "a gather chunk fits the
 
 typedef unsigned int rel_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int rel_v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t rel_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // |x| as bits, 0 for Inf / NaN
 __device__ __forceinline__ uint32_t rel_mag(uint32_t bits)
@@ -62,40 +66,45 @@ __device__ __forceinline__ Params rel_params(uint32_t a, uint32_t rel_bits, uint
   return Params{1u, 16658u, maxprec, minexp};
 }
 
+// Where a tensor's parameter set comes from. Both kernels below are templates over it, called once per workgroup
+// (uniform: the direct kernel) or once per block (raw, then params: the gather kernel, whose lanes past the chunk code a
+// zero block under params(0)).
+//   RelFromAbsmax   the relative form: rel_params of the tensor's slot of absmax. The slot's address is uniform, so the
+//                   load is scalar and none that rt_var_chunk's hand-counted vmcnt waits count.
+//   RelFromWord     the fitted form (gcow_roundtrip_rel_fitted_device): minexp = clamp(d_minexp[seg * stride], -154, 133),
+//                   the word read when the kernel runs. Direct: seg has gone through readfirstlane, so the address is
+//                   uniform, and fitted_params_dev<true> has the word waited for ahead of rt_var_chunk's first asm row
+//                   load (the rule is stated there, var1d_prep.h). Gather: one word per lane, the same clamp.
+struct RelFromAbsmax {
+  const uint32_t* __restrict__ absmax;
+  uint32_t rel_bits, maxprec;
+  __device__ __forceinline__ Params uniform(uint32_t seg) const
+  {
+    return rel_params(rel_uniform(absmax[seg]), rel_bits, maxprec);
+  }
+  __device__ __forceinline__ uint32_t raw(uint32_t seg) const { return absmax[seg]; }
+  __device__ __forceinline__ Params params(uint32_t raw) const { return rel_params(raw, rel_bits, maxprec); }
+};
+
+struct RelFromWord {
+  const int32_t* __restrict__ d_minexp;
+  uint32_t stride, maxprec;  // stride in 4-byte words: 4 for an array of gcow_fit, 1 for packed words
+  __device__ __forceinline__ Params uniform(uint32_t seg) const
+  {
+    return fitted_params_dev<true>(maxprec, d_minexp + (uint64_t)seg * stride);
+  }
+  __device__ __forceinline__ uint32_t raw(uint32_t seg) const { return (uint32_t)d_minexp[(uint64_t)seg * stride]; }
+  __device__ __forceinline__ Params params(uint32_t raw) const
+  {
+    return Params{1u, 16658u, maxprec, min(max((int)raw, kFitMinExpLo), kFitMinExpHi)};
+  }
+};
+static_assert(sizeof(RelFromAbsmax) == 16 && sizeof(RelFromWord) == 16, "one pointer and two words of kernel arguments");
+
 __global__ __launch_bounds__(256) void k_rel_init(uint32_t* __restrict__ absmax, uint32_t nsegs, uint64_t* total)
 {
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nsegs; i += gridDim.x * 256u) absmax[i] = 0u;
   if (total && blockIdx.x == 0 && threadIdx.x == 0) *total = 0ull;
-}
-
-// ------------------------------------------------------------------------------------------------ gather blocks
-// Virtual block vb0 + i of a gather chunk: the last piece that starts at or before it (at most log2(pieces of the
-// chunk) steps), then the block's place in that piece's tensor.
-struct RelBlock {
-  const char* in;
-  char* out;
-  uint64_t x0;  // the block's first value in its tensor
-  uint32_t nv;  // real values, 1 .. 4
-  uint32_t seg;
-};
-
-__device__ __forceinline__ RelBlock rel_locate(const RtRelGather& c, const RtRelPiece* __restrict__ pieces, uint32_t i)
-{
-  const uint32_t v = c.vb0 + i;
-  uint32_t lo = c.p_lo, hi = c.p_hi;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (pieces[mid].vb <= v) lo = mid;
-    else hi = mid - 1u;
-  }
-  const RtRelPiece e = pieces[lo];
-  RelBlock b;
-  b.in = (const char*)e.in;
-  b.out = (char*)e.out;
-  b.x0 = 4ull * ((uint64_t)e.b0 + (v - e.vb));
-  b.nv = (uint32_t)min<uint64_t>(4, e.n - b.x0);
-  b.seg = e.seg;
-  return b;
 }
 
 // ------------------------------------------------------------------------------------------------ the maximum
@@ -166,10 +175,9 @@ __global__ __launch_bounds__(256) void k_rel_absmax(const RtRelDirect* __restric
 
 // ------------------------------------------------------------------------------------------------ direct chunks
 // Lanes past the chunk's nb blocks read zeros and have their stores dropped by the range check (rt_var_chunk).
-template <int DT_IN, int DT_OUT, bool COUNT, int U>
-__global__ __launch_bounds__(256) void k_roundtrip_rel_direct(const RtRelDirect* __restrict__ desc,
-                                                              const uint32_t* __restrict__ absmax, uint32_t rel_bits,
-                                                              uint32_t maxprec, uint64_t* total)
+template <int DT_IN, int DT_OUT, bool COUNT, int U, class PS>
+__global__ __launch_bounds__(256) void k_roundtrip_rel_direct(const RtRelDirect* __restrict__ desc, PS ps,
+                                                              uint64_t* total)
 {
   __shared__ uint32_t cnt_sh[4];
   const RtRelDirect* d = desc + blockIdx.x;
@@ -184,19 +192,18 @@ __global__ __launch_bounds__(256) void k_roundtrip_rel_direct(const RtRelDirect*
   rin.w = 0x00020000;
   const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(((uint64_t)ohi << 32) | olo), 0, (int)(nb * rt_row_bytes<DT_OUT>()), 0x00020000);
-  // the tensor's slot: the descriptor's address is uniform, so is this load's
-  const Params p = rel_params(rel_uniform(absmax[rel_uniform(d->seg)]), rel_bits, maxprec);
+  // the tensor's slot or word: the descriptor's address is uniform, so is this load's
+  const Params p = ps.uniform(rel_uniform(d->seg));
   const uint32_t lsum = rt_var_chunk<DT_IN, DT_OUT, COUNT, U>(rin, rout, threadIdx.x, nb, p);
   if constexpr (COUNT) rt_count(lsum, cnt_sh, total);
 }
 
 // ------------------------------------------------------------------------------------------------ gather chunks
 // Lanes past the chunk code a zero block and neither load nor store: the block function runs with every lane active.
-template <int DT_IN, int DT_OUT, int U>
+template <int DT_IN, int DT_OUT, int U, class PS>
 __global__ __launch_bounds__(256) void k_roundtrip_rel_gather(const RtRelGather* __restrict__ chunks,
-                                                              const RtRelPiece* __restrict__ pieces,
-                                                              const uint32_t* __restrict__ absmax, uint32_t rel_bits,
-                                                              uint32_t maxprec, uint64_t* total)
+                                                              const RtRelPiece* __restrict__ pieces, PS ps,
+                                                              uint64_t* total)
 {
   __shared__ uint32_t cnt_sh[4];
   constexpr uint32_t OE = DT_OUT == DT_BF16 ? 2u : 4u;
@@ -212,7 +219,7 @@ __global__ __launch_bounds__(256) void k_roundtrip_rel_gather(const RtRelGather*
     if (act) {
       const RelBlock b = rel_locate(c, pieces, i);
       nv = b.nv;
-      a = absmax[b.seg];
+      a = ps.raw(b.seg);
       o = b.out + b.x0 * OE;
 #pragma unroll
       for (uint32_t x = 0; x < 4u; x++)
@@ -222,7 +229,7 @@ __global__ __launch_bounds__(256) void k_roundtrip_rel_gather(const RtRelGather*
       if (nv < 3u) f[2] = nv == 2u ? f[1] : f[0];
       if (nv < 4u) f[3] = f[0];
     }
-    const Params p = rel_params(a, rel_bits, maxprec);
+    const Params p = ps.params(a);
     const uint32_t len = rt_var_code(f, p, d);
     lsum += act ? len : 0u;
 #pragma unroll
@@ -236,24 +243,29 @@ __global__ __launch_bounds__(256) void k_roundtrip_rel_gather(const RtRelGather*
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-template <int DT_IN, int DT_OUT>
-static void launch_rel_t(const RtRelHeader& h, const char* d_plan, uint32_t rel_bits, uint32_t maxprec,
-                         uint32_t* absmax, uint64_t* total, hipStream_t st)
+template <int DT_IN, int DT_OUT, class PS>
+static void launch_rel_coders(const RtRelHeader& h, const char* d_plan, PS ps, uint64_t* total, hipStream_t st)
 {
   constexpr int U = GCOW_RT_U;
   const RtRelDirect* dd = (const RtRelDirect*)(d_plan + h.off_direct);
   const RtRelGather* gg = (const RtRelGather*)(d_plan + h.off_gather);
   const RtRelPiece* pp = (const RtRelPiece*)(d_plan + h.off_pieces);
-  k_rel_absmax<DT_IN, U><<<h.ngather + h.ndirect, 256, 0, st>>>(dd, gg, h.ngather, pp, absmax);
   if (h.ndirect) {
-    if (total)
-      k_roundtrip_rel_direct<DT_IN, DT_OUT, true, U><<<h.ndirect, 256, 0, st>>>(dd, absmax, rel_bits, maxprec, total);
-    else
-      k_roundtrip_rel_direct<DT_IN, DT_OUT, false, U><<<h.ndirect, 256, 0, st>>>(dd, absmax, rel_bits, maxprec,
-                                                                                nullptr);
+    if (total) k_roundtrip_rel_direct<DT_IN, DT_OUT, true, U, PS><<<h.ndirect, 256, 0, st>>>(dd, ps, total);
+    else k_roundtrip_rel_direct<DT_IN, DT_OUT, false, U, PS><<<h.ndirect, 256, 0, st>>>(dd, ps, nullptr);
   }
-  if (h.ngather)
-    k_roundtrip_rel_gather<DT_IN, DT_OUT, U><<<h.ngather, 256, 0, st>>>(gg, pp, absmax, rel_bits, maxprec, total);
+  if (h.ngather) k_roundtrip_rel_gather<DT_IN, DT_OUT, U, PS><<<h.ngather, 256, 0, st>>>(gg, pp, ps, total);
+}
+
+template <int DT_IN, int DT_OUT>
+static void launch_rel_t(const RtRelHeader& h, const char* d_plan, uint32_t rel_bits, uint32_t maxprec,
+                         uint32_t* absmax, uint64_t* total, hipStream_t st)
+{
+  const RtRelDirect* dd = (const RtRelDirect*)(d_plan + h.off_direct);
+  const RtRelGather* gg = (const RtRelGather*)(d_plan + h.off_gather);
+  const RtRelPiece* pp = (const RtRelPiece*)(d_plan + h.off_pieces);
+  k_rel_absmax<DT_IN, GCOW_RT_U><<<h.ngather + h.ndirect, 256, 0, st>>>(dd, gg, h.ngather, pp, absmax);
+  launch_rel_coders<DT_IN, DT_OUT>(h, d_plan, RelFromAbsmax{absmax, rel_bits, maxprec}, total, st);
 }
 
 hipError_t launch_roundtrip_rel1d(const RtRelHeader& h, const void* d_plan, uint32_t rel_bits, uint32_t maxprec,
@@ -270,6 +282,26 @@ hipError_t launch_roundtrip_rel1d(const RtRelHeader& h, const void* d_plan, uint
     } else {
       if (h.out_dtype == DT_F32) launch_rel_t<DT_BF16, DT_F32>(h, dp, rel_bits, maxprec, absmax, total, st);
       else launch_rel_t<DT_BF16, DT_BF16>(h, dp, rel_bits, maxprec, absmax, total, st);
+    }
+  }
+  return hipGetLastError();
+}
+
+// The fitted form: *total = 0 in stream order (k_rel_init over no slots), then the two coders under RelFromWord.
+hipError_t launch_roundtrip_rel1d_fitted(const RtRelHeader& h, const void* d_plan, uint32_t maxprec,
+                                         const int32_t* d_minexp, uint32_t stride_words, uint64_t* total, void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  if (total) k_rel_init<<<1, 256, 0, st>>>(nullptr, 0u, total);
+  if (h.ndirect + h.ngather) {
+    const char* dp = (const char*)d_plan;
+    const RelFromWord ps{d_minexp, stride_words, maxprec};
+    if (h.in_dtype == DT_F32) {
+      if (h.out_dtype == DT_F32) launch_rel_coders<DT_F32, DT_F32>(h, dp, ps, total, st);
+      else launch_rel_coders<DT_F32, DT_BF16>(h, dp, ps, total, st);
+    } else {
+      if (h.out_dtype == DT_F32) launch_rel_coders<DT_BF16, DT_F32>(h, dp, ps, total, st);
+      else launch_rel_coders<DT_BF16, DT_BF16>(h, dp, ps, total, st);
     }
   }
   return hipGetLastError();

@@ -135,7 +135,20 @@ class GcowHookState:
     the bucket alone. The codec must also have rate_table_residual and encode_residual_fitted, else ValueError.
     Combined with `compress_mean`, registered with compressed_sharded_hook, or roundtrip_hook with `error_feedback`:
     ValueError -- those encodes are other kernel families. A codec without rate_table,
-    fit_device, encode_fitted and roundtrip_fitted: ValueError. Unset (the default): nothing changes."""
+    fit_device, encode_fitted and roundtrip_fitted: ValueError. Unset (the default): nothing changes.
+
+    `per_tensor_budget` (roundtrip_hook only, and only together with `target_bits`): the budget is per gradient, not
+    per bucket. After the mean all-reduce every parameter's gradient in the bucket (bucket.gradients(), views of the
+    buffer) is round-tripped in place as a field of its own, under the finest tolerance whose stream takes at most
+    floor(target_bits * n_s) bits: one pass writes a rate table per gradient, one kernel fits them all and the round
+    trip reads each gradient's minexp from its record (codec.TensorListFittedPerTensor through the codec's
+    roundtrip_fitted_per_tensor, cached per bucket). It is always fitted on the device -- nothing is read on the host,
+    whatever `fit_on_device` says -- and `fit_record(index)` is the int64[S, 2] tensor of the bucket's records. A quiet
+    layer keeps its own tolerance and a loud one cannot take its bits; fits stop at minexp -94 (include/gcow.h).
+    `params` supplies maxprec. The bucket must be fp32 or bf16. ValueError: without `target_bits`; with
+    `relative_bits` (both choose the tolerance), `error_feedback` or `compress_mean`; registered with a wire hook,
+    whose decoder would need the per-tensor minexp on the wire; a codec without roundtrip_fitted_per_tensor. Unset
+    (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -154,6 +167,8 @@ class GcowHookState:
     target_bits: float | None = None
     # with target_bits: fit on the device, in the step that is encoded (class docstring)
     fit_on_device: bool = False
+    # roundtrip_hook with target_bits: a budget per gradient tensor, fitted on the device (class docstring)
+    per_tensor_budget: bool = False
     _fit_records: dict = field(default_factory=dict, repr=False)  # bucket index -> the device gcow_fit record
     _fits: dict = field(default_factory=dict, repr=False)  # bucket index -> (numel, fitted minexp)
     _worker: object = field(default=None, repr=False)
@@ -239,6 +254,8 @@ class GcowHookState:
         if self.target_bits is None:
             if self.fit_on_device:
                 raise ValueError("fit_on_device fits target_bits on the device: set target_bits")
+            if self.per_tensor_budget:
+                raise ValueError("per_tensor_budget gives every gradient target_bits bits per value: set target_bits")
             return
         if not _codec.is_nobudget(self.params) or _codec.is_fixed(self.params):
             raise ValueError("target_bits fits accuracy mode: params must be a variable-rate set without a block "
@@ -361,6 +378,8 @@ def _fit_next(state: GcowHookState, table: torch.Tensor, index, n: int, world: i
     state._fits[index] = (n, me)
 
 
+_PER_TENSOR_WIRE = ("per_tensor_budget is for roundtrip_hook: a stream coded under a minexp per tensor needs them on "
+                    "the wire to be decoded, which the wire hooks do not send")
 _RELATIVE_WIRE = ("relative_bits is for roundtrip_hook: a stream coded under per-tensor exponents needs them on the "
                   "wire to be decoded, which the wire hooks do not send")
 
@@ -370,10 +389,13 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
     `roundtrip` call on an fp32 / bf16 bucket when the codec has one, else encode followed by decode."""
     if state.error_feedback:
         raise ValueError("error_feedback is for the wire hooks (compressed_allgather_hook, compressed_sharded_hook): "
-                         "roundtrip_hook applies its loss after the reduction, identically on every rank")
+                         "roundtrip_hook applies its loss after the reduction, identically on every rank"
+                         + (" (per_tensor_budget has no residual form)" if state.per_tensor_budget else ""))
     if state.compress_mean:
         raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
                          "roundtrip_hook puts no mean shard on the wire")
+    if state.per_tensor_budget and state.relative_bits is not None:
+        raise ValueError("per_tensor_budget (with target_bits) and relative_bits both choose the tolerance: set one")
     state.check_target()
     group = state.process_group
     buf = bucket.buffer()
@@ -385,11 +407,24 @@ def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.T
             raise ValueError("relative_bits needs a codec with roundtrip_relative (gcow_amd.dist.DeviceCodec)")
         if buf.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("relative_bits takes fp32 or bf16 buckets, got %s" % buf.dtype)
+    ptb = state.per_tensor_budget
+    if ptb:
+        if not hasattr(cdc, "roundtrip_fitted_per_tensor"):
+            raise ValueError("per_tensor_budget needs a codec with roundtrip_fitted_per_tensor "
+                             "(gcow_amd.dist.DeviceCodec)")
+        if buf.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("per_tensor_budget takes fp32 or bf16 buckets, got %s" % buf.dtype)
     world = dist.get_world_size(group)
     fut = dist.all_reduce(buf.div_(world), group=group, async_op=True).get_future()
 
     def lossy(f):
         t = f.value()[0]
+        if ptb:  # each parameter's view of the bucket, in place, under its own budget: tables -> fits -> round trip
+            bidx = bucket.index() if hasattr(bucket, "index") else None
+            plan = cdc.roundtrip_fitted_per_tensor(bucket.gradients(), state.target_bits,
+                                                   maxprec=state.params.maxprec, slot=("per_tensor", bidx))
+            state._fit_records[bidx] = getattr(plan, "fits", None)
+            return t
         if rel is not None:  # each parameter's view of the bucket, in place, under its own tolerance
             cdc.roundtrip_relative(bucket.gradients(), rel, maxprec=state.params.maxprec,
                                    slot=("rel", bucket.index()))
@@ -484,6 +519,8 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
                          "compressed_allgather_hook decodes every rank's stream on every rank and sends no mean")
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
+    if state.per_tensor_budget:
+        raise ValueError(_PER_TENSOR_WIRE)
     state.check_target()
     cdc = state.get_codec()
     fod = state.check_fit_on_device(cdc, "compressed_allgather_hook")  # before any collective
@@ -620,6 +657,8 @@ def compressed_sharded_hook(state: GcowHookState, bucket) -> torch.futures.Futur
     decode_mean and encode), and the bucket ends as decode(encode(mean)) under state.mean_params on every rank."""
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
+    if state.per_tensor_budget:
+        raise ValueError(_PER_TENSOR_WIRE)
     state.check_target()
     state.check_fit_on_device(state.get_codec(), "compressed_sharded_hook")
     group = state.process_group

@@ -135,6 +135,20 @@ class DeviceCodec:
         self._evict_idle()
         return ent[0](tensors)
 
+    def roundtrip_fitted_per_tensor(self, tensors, bits_per_value: float, maxprec: int = 64, slot=None):
+        """Every tensor of the list round-tripped in place under its own bit budget of floor(bits_per_value * n_s)
+        bits, fitted on the device (codec.TensorListFittedPerTensor: tables, fits, round trip, no host read). The plan
+        object (pinned plan, device copy, tables, records, budgets) is cached per (slot, bits_per_value, maxprec,
+        device) under the encoders' idleness rule, so a list that stays where it is plans once. Returns the plan
+        object (`fits`, `bits`, `tables`)."""
+        from . import codec
+        tensors = list(tensors)
+        dev = tensors[0].device if tensors else None
+        key = (slot, float(bits_per_value), int(maxprec), dev, "fitted_per_tensor")
+        plan = self._cached(key, lambda: codec.TensorListFittedPerTensor(bits_per_value, maxprec))
+        plan(tensors)
+        return plan
+
     def rate_table(self, x: torch.Tensor, maxprec: int = 64, slot=None) -> torch.Tensor:
         """The rate table of the flattened bucket x (codec.RateTable): int64[288] on x's device, entry t the bits
         `encode` reports under expert(1, 16658, maxprec, -154 + t). The table and workspace are cached per (slot,

@@ -557,8 +557,8 @@ gcow_status gcow_roundtrip_fitted_device(const zfp_input* field, uint32_t maxpre
  * Accuracy mode under a bit budget over a tensor list: the rate table and the fitted round trip of the concatenation
  * X = cat(t_0 ... t_{S-1}) (N values, as in gcow_roundtrip_list_device's contract), every tensor read and written
  * where it lies. Table, gcow_rate_table_fit_device and round trip go on one stream with no host read, and can be
- * captured into one graph. The budget is one for the whole list (one table for the concatenation); a table per tensor
- * is not offered.
+ * captured into one graph. The budget is one for the whole list (one table for the concatenation); a budget per tensor
+ * is the block after this one (gcow_rate_table_rel_device).
  *
  * The plan. Both calls take a plan of gcow_roundtrip_list_plan as it is (h_plan, d_plan, plan_bytes as
  * gcow_roundtrip_list_device's), made for any set WITHOUT A BLOCK BUDGET: minbits <= 1 and maxbits >= 160
@@ -590,6 +590,54 @@ gcow_status gcow_rate_table_list_device(const void* h_plan, const void* d_plan, 
 gcow_status gcow_roundtrip_list_fitted_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
                                               uint32_t maxprec, const int32_t* d_minexp, uint64_t* d_total_bits,
                                               void* hip_stream);
+
+/*
+ * Accuracy mode under a bit budget PER TENSOR of a list: every tensor is a field of its own, as in
+ * gcow_roundtrip_rel_device, with its own rate table, its own budget and its own fitted minexp, so that the loud
+ * tensors of a gradient list neither decide the quiet ones' tolerance nor take their bits. Tables, fits and round trip
+ * go on one stream with no host read in between, allocate nothing and can be captured into one graph that follows the
+ * data it is replayed on. 1-D, dtype_float / dtype_bf16.
+ *
+ * The plan. All three plan calls take a plan of gcow_roundtrip_rel_plan as it is (h_plan, d_plan, plan_bytes as
+ * gcow_roundtrip_rel_device's; S = nsegs tensors in the caller's numbering, empty ones included).
+ *
+ * gcow_rate_table_rel_workspace_bytes: the workspace of the table call: 0 for a NULL, short or foreign plan, else
+ *   positive and a function of S only.
+ * gcow_rate_table_rel_device: d_tables is DEVICE uint64[S][288]. Row s is exactly what gcow_rate_table_device writes for
+ *   tensor s as a field of its own -- its blocks counted from its first value, its partial last block padded as the
+ *   encoder pads it -- i.e. row s, entry t is the *d_total_bits of gcow_roundtrip_device(t_s, {1, 16658, maxprec,
+ *   -154 + t}). An empty tensor gives an all-zero row. Only the plan's input pointers are read. The tables are written
+ *   whole and nothing past them; neither they nor the workspace (8-byte aligned) need zeroing by the caller, and the
+ *   workspace is zeroed by a kernel in stream order, not by a memset node. Integer sums only: the same bits run to run.
+ * gcow_rate_table_fit_batch_device: one workgroup per table. d_tables: DEVICE uint64[ntables][288]; d_budgets: DEVICE
+ *   uint64[ntables]; d_fits: DEVICE gcow_fit[ntables]. Record s = the smallest minexp in [max(minexp_floor, -154), 133]
+ *   whose entry of table s is <= d_budgets[s], that entry, status 0; where no such entry fits, {133, 1, table_s[287]}.
+ *   With minexp_floor = -154 and ntables = 1 it is gcow_rate_table_fit_device with the budget in device memory. The
+ *   floor exists for the reason gcow_roundtrip_rel_device has one (above: "neither clamp is cosmetic"): at
+ *   minexp >= -94 every block whose values all cast to INT_MIN (emax <= -98) has precision 0 and decodes to +0, not to
+ *   garbage of twice its magnitude; a generous budget would otherwise fit a tensor of scale 1e-40 below that. The
+ *   relative form's cap for a maximum in the top binade is NOT reproduced: a fit knows bits, not the maximum. A tensor
+ *   of scale 3e38 behaves as gcow_roundtrip_fitted_device behaves on it: under a coarse fitted minexp finite values
+ *   near the maximum may decode to Inf. ntables = 0 does nothing.
+ * gcow_roundtrip_rel_fitted_device: tensor s is coded under m_s = clamp(d_minexp[s * minexp_stride_words], -154, 133),
+ *   the words (DEVICE int32, 4-byte aligned, unchanged by the call) read ON THE DEVICE when the kernels run: a stride
+ *   of 4 words walks an array of gcow_fit, a stride of 1 packed words. out_s is bit for bit what
+ *   gcow_roundtrip_fitted_device(t_s, maxprec, &word_s, ...) writes, and *d_total_bits (optional DEVICE uint64) the sum
+ *   over s of its bit counts. Dtypes, in place, and "only real values are written, nothing outside
+ *   [out_s, out_s + n_s)" as gcow_roundtrip_rel_device. An empty list returns GCOW_OK and writes *d_total_bits = 0.
+ * GCOW_ERR_INVALID, all decided on the host before any launch: a NULL, short (plan_bytes) or foreign h_plan; with
+ * S > 0 (ntables > 0) a NULL or misaligned (8 bytes) d_plan, d_tables, d_workspace, d_budgets or d_fits, or a NULL or
+ * misaligned (4 bytes) d_minexp; a misaligned d_total_bits; a workspace below the query; a stride of 0; maxprec as
+ * check_params has it for {1, 16658, maxprec, 0}.
+ */
+size_t gcow_rate_table_rel_workspace_bytes(const void* h_plan, size_t plan_bytes);
+gcow_status gcow_rate_table_rel_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                       uint64_t* d_tables, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+gcow_status gcow_rate_table_fit_batch_device(const uint64_t* d_tables, size_t ntables, const uint64_t* d_budgets,
+                                             int32_t minexp_floor, gcow_fit* d_fits, void* hip_stream);
+gcow_status gcow_roundtrip_rel_fitted_device(const void* h_plan, const void* d_plan, size_t plan_bytes,
+                                             uint32_t maxprec, const int32_t* d_minexp, uint32_t minexp_stride_words,
+                                             uint64_t* d_total_bits, void* hip_stream);
 
 /*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to

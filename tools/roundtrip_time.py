@@ -31,7 +31,11 @@ usage: roundtrip_time.py --relative [--only NAME]
 the composed flow torch.cat + rate table + device fit + roundtrip_fitted + one copy_ per tensor against
 codec.TensorListFitted, at 8.0 and 2.5 bits per value, with the table pass, the fit and the round trip of both broken
 out. Medians over interleaved rounds with their spread.
-usage: roundtrip_time.py --fitted-list [--only NAME] [--rounds 9]"""
+usage: roundtrip_time.py --fitted-list [--only NAME] [--rounds 9]
+
+--fitted-per-tensor: a bit budget per tensor (codec.TensorListFittedPerTensor) on that list against one budget for the
+list, the relative tolerance and the per-tensor loop of single calls (fitted_per_tensor_leg's docstring).
+usage: roundtrip_time.py --fitted-per-tensor [--only NAME] [--rounds 9]"""
 import json
 import math
 import os
@@ -365,6 +369,135 @@ def fitted_list_leg():
         print(json.dumps(res), flush=True)
 
 
+def fitted_per_tensor_leg():
+    """A bit budget per tensor (codec.TensorListFittedPerTensor) on the ResNet-50-shaped fp32 list of fitted_list_leg,
+    against the three forms it stands beside: one budget for the list (codec.TensorListFitted), the relative
+    tolerance (codec.TensorListRelative, 8 bits) and the loop a caller had to write for a budget per tensor -- per
+    tensor a kept codec.RateTable, codec.fit_device into a kept record and codec.roundtrip_fitted. All four write
+    outputs of their own from inputs that are never written, allocate nothing in a timed call and read nothing on the
+    host. Checked first: the per-tensor form and the loop give the same outputs, records and summed bits. Then the
+    four forms, eager and captured into a graph, the two table passes (one table for the list; a table per tensor:
+    the same bytes read), the batch fit and the fitted round trip are timed in rounds that take the parts in turn in
+    one process, as fitted_list_leg does: 3 untimed and 20 timed launches per part and round, mean HIP-event time;
+    reported are the median over the rounds and [min, max]."""
+    rounds = arg("--rounds", 9)
+    shapes = resnet50_shapes()
+    total = sum(math.prod(s) for s in shapes)
+    src = torch.empty(total, dtype=torch.float32, device="cuda")
+    codec.fill_normal(src, 1e-3, seed=0x67636F77, inject=True)
+    offs = [0]
+    for s in shapes:
+        offs.append(offs[-1] + math.prod(s))
+    ts = [src[offs[i]:offs[i + 1]].clone().view(s) for i, s in enumerate(shapes)]
+    flats = [t.view(-1) for t in ts]
+    outs = {k: [torch.empty_like(t) for t in ts] for k in "pblr"}
+    flat_l = [o.view(-1) for o in outs["l"]]
+    for bpv in (8.0, 2.5):
+        name = "fitted_per_tensor_resnet50_fp32_%gbpv" % bpv
+        if only and name != only:
+            continue
+        bits = {k: torch.zeros(1, dtype=torch.int64, device="cuda") for k in "pbr"}
+        plan_p = codec.TensorListFittedPerTensor(bpv)
+        plan_b = codec.TensorListFitted(bpv)
+        plan_r = codec.TensorListRelative(8)
+        tabs = [codec.RateTable(f.numel(), torch.float32) for f in flats]
+        recs = torch.zeros((len(ts), codec.FIT_WORDS), dtype=torch.int64, device="cuda")
+        bits_l = torch.zeros(len(ts), dtype=torch.int64, device="cuda")
+        budgets = [int(math.floor(bpv * f.numel())) for f in flats]
+        cur = {"st": st}  # the stream the forms launch on: the timing stream, or the capturing one
+
+        def p_fn():
+            plan_p(ts, outs["p"], bits["p"], cur["st"])
+
+        def b_fn():
+            plan_b(ts, outs["b"], bits["b"], cur["st"])
+
+        def r_fn():
+            plan_r(ts, outs["r"], None, bits["r"], cur["st"])
+
+        def l_fn():
+            for i, f in enumerate(flats):
+                tabs[i](f, 64, cur["st"])
+                codec.fit_device(tabs[i].table, budgets[i], recs[i], cur["st"])
+                codec.roundtrip_fitted(f, recs[i], 64, out=flat_l[i], bits=bits_l[i:i + 1], stream=cur["st"])
+
+        # the parts go to the C ABI with the plans as the whole calls left them (fitted_list_leg says why)
+        def b_table():
+            plan_b._table(st)
+
+        def p_tables():
+            plan_p._tables(len(ts), st)
+
+        def p_fit():
+            codec.fit_device_batch(plan_p.tables, plan_p.budgets, plan_p.minexp_floor, plan_p.fits, st)
+
+        def p_rt():
+            plan_p.L.gcow_roundtrip_rel_fitted_device(plan_p._h.data_ptr(), plan_p._d.data_ptr(), plan_p._used, 64,
+                                                      plan_p.fits.data_ptr(), 4, bits["p"].data_ptr(), st.cuda_stream)
+
+        def captured(fn):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                cur["st"] = torch.cuda.current_stream()
+                fn()
+            cur["st"] = st
+            return g.replay
+
+        for fn in (p_fn, b_fn, r_fn, l_fn):
+            fn()
+        torch.cuda.synchronize()
+        # the floor is out of reach for this data, so the loop (which has none) must agree
+        same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs["p"], outs["l"]))
+        same = same and torch.equal(plan_p.fits, recs) and int(bits["p"].item()) == int(bits_l.sum().item())
+        same = same and all(torch.equal(plan_p.tables[i], tabs[i].table) for i in range(len(ts)))
+        fits = plan_p.fits.cpu()
+        mes = sorted(int(w) & 0xFFFFFFFF for w in fits[:, 0].tolist())
+        mes = [m - (1 << 32) if m >> 31 else m for m in mes]
+        stats = plan_p.stats()
+        res = {"config": name, "tensors": len(shapes), "n": total, "bits_per_value": bpv, "same_as_loop": bool(same),
+               "fitted_minexp_min": min(mes), "fitted_minexp_max": max(mes),
+               "fit_status_1": int(sum((int(w) >> 32) & 1 for w in fits[:, 0].tolist())),
+               "stream_bits_per_value": round(int(bits["p"].item()) / total, 3),
+               "one_budget_minexp": codec.read_fit(plan_b.fit)[0],
+               "direct_chunks": int(stats.direct_chunks), "gather_chunks": int(stats.gather_chunks), "rounds": rounds}
+        graphs = {k: captured(fn) for k, fn in (("p", p_fn), ("b", b_fn), ("r", r_fn), ("l", l_fn))}
+        for g in graphs.values():
+            g()
+        torch.cuda.synchronize()
+        same = same and all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs["p"], outs["l"]))
+        res["same_as_loop"] = bool(same)
+        parts = [("per_tensor", p_fn), ("one_budget", b_fn), ("relative", r_fn), ("loop", l_fn),
+                 ("per_tensor_graph", graphs["p"]), ("one_budget_graph", graphs["b"]), ("relative_graph", graphs["r"]),
+                 ("loop_graph", graphs["l"]), ("one_budget_table", b_table), ("per_tensor_tables", p_tables),
+                 ("per_tensor_fit", p_fit), ("per_tensor_roundtrip", p_rt)]
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.25:
+            p_fn()
+            b_fn()
+            torch.cuda.synchronize()
+        got = {k: [] for k, _ in parts}
+        for _ in range(rounds):
+            for k, fn in parts:
+                got[k].append(timed(fn, 3, 20))
+        for k, v in got.items():
+            v.sort()
+            res[k + "_ms"] = {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+        res["tables_over_one_table"] = round(res["per_tensor_tables_ms"]["median"] / res["one_budget_table_ms"]["median"], 3)
+        res["tables_within_spread"] = bool(res["per_tensor_tables_ms"]["min"] <= res["one_budget_table_ms"]["max"]
+                                           and res["one_budget_table_ms"]["min"] <= res["per_tensor_tables_ms"]["max"])
+        res["loop_over_per_tensor"] = round(res["loop_ms"]["median"] / res["per_tensor_ms"]["median"], 3)
+        res["loop_over_per_tensor_graph"] = round(res["loop_graph_ms"]["median"] / res["per_tensor_graph_ms"]["median"], 3)
+        res["per_tensor_over_one_budget_graph"] = round(res["per_tensor_graph_ms"]["median"]
+                                                        / res["one_budget_graph_ms"]["median"], 3)
+        res["per_tensor_over_relative_graph"] = round(res["per_tensor_graph_ms"]["median"]
+                                                      / res["relative_graph_ms"]["median"], 3)
+        res["plan_rebuilds"] = plan_p.rebuilds
+        print(json.dumps(res), flush=True)
+
+
+if "--fitted-per-tensor" in sys.argv:
+    fitted_per_tensor_leg()
+    sys.exit(0)
 if "--list" in sys.argv:
     list_leg()
     sys.exit(0)
