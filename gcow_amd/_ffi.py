@@ -73,6 +73,12 @@ class RoundtripRelStats(C.Structure):
                 ("direct_chunks", C.c_uint64), ("gather_chunks", C.c_uint64), ("used_bytes", C.c_uint64)]
 
 
+class SegStats(C.Structure):
+    """gcow_seg_stats (include/gcow.h)."""
+    _fields_ = [("total_values", C.c_uint64), ("virtual_blocks", C.c_uint64), ("segments", C.c_uint64),
+                ("tiles", C.c_uint64), ("uniform_tiles", C.c_uint64), ("used_bytes", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -145,6 +151,17 @@ def load():
         "gcow_rate_table_fit_batch_device": (i32, [vp, sz, vp, i32, vp, vp]),
         "gcow_roundtrip_rel_fitted_device": (i32, [vp, vp, sz, u32, vp, u32, vp, vp]),
         "gcow_encode_residual_fitted_device": (i32, [pi, u32, vp, vp, vp, vp, sz, vp, vp, sz, vp, u32, vp]),
+        "gcow_seg_plan_bytes": (sz, [sz, u64]),
+        "gcow_seg_plan": (i32, [P(u64), sz, i32, vp, sz, P(sz)]),
+        "gcow_seg_plan_stats": (i32, [vp, sz, P(SegStats)]),
+        "gcow_seg_plan_segment": (i32, [vp, sz, u64, P(u64), P(u64), P(u64)]),
+        "gcow_seg_plan_tile": (i32, [vp, sz, u64, P(u64), P(i32)]),
+        "gcow_encode_seg_max_output_bytes": (sz, [vp, sz]),
+        "gcow_encode_seg_workspace_bytes": (sz, [vp, sz]),
+        "gcow_encode_seg_index_entries": (sz, [vp, sz, u32]),
+        "gcow_encode_seg_device": (i32, [vp, vp, sz, vp, u32, vp, u32, vp, sz, vp, vp, sz, vp, u32, vp]),
+        "gcow_decode_mean_seg_device": (i32, [vp, vp, sz, u32, vp, u32, u64, vp, sz, u64, u32, vp, u64, u32, vp, i32,
+                                              vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),
         "gcow_stitch_device": (i32, [vp, u64, vp, u64, vp]),
         "gcow_stitch_shards_device": (i32, [vp, u64, vp, u64, vp, u32, vp]),

@@ -1215,6 +1215,209 @@ def roundtrip_gradients_fitted_per_tensor(parameters, bits_per_value: float, max
     return plan
 
 
+# ------------------------------------------------------------------------------ segmented fields: a minexp per tensor
+class SegmentPlan:
+    """The plan of a segmented field (gcow_seg_plan; include/gcow.h "Segmented fields"): a contiguous buffer of
+    sum(counts) values of `dtype` cut into len(counts) tensors in order. It holds no pointers and depends on neither
+    maxprec nor the minexp words, so one plan serves every buffer of the shape, the encode and the decode. The host plan
+    is `h` (int64, `used` bytes); with `device` its copy `d` is made at once (else by `to`)."""
+
+    def __init__(self, counts, dtype=torch.float32, device=None):
+        self.L = load()
+        self.counts = tuple(int(c) for c in counts)
+        if any(c < 0 for c in self.counts):
+            raise GcowError("SegmentPlan: negative count")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise GcowError("SegmentPlan: dtype %s not supported (float32, bfloat16)" % dtype)
+        self.dtype, self.n = dtype, sum(self.counts)
+        ns = len(self.counts)
+        need = self.L.gcow_seg_plan_bytes(ns, self.n)
+        self.h = torch.zeros((need + 7) // 8, dtype=torch.int64)
+        cnt = (C.c_uint64 * max(ns, 1))(*self.counts)
+        used = C.c_size_t(0)
+        check(self.L.gcow_seg_plan(cnt, ns, DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_FLOAT, self.h.data_ptr(),
+                                   self.h.numel() * 8, C.byref(used)), "gcow_seg_plan")
+        self.used = int(used.value)
+        self.d = None
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        device = _device_of(device)
+        if self.d is None or self.d.device != device:
+            self.d = self.h.to(device)
+        return self
+
+    def stats(self):
+        from ._ffi import SegStats
+        s = SegStats()
+        check(self.L.gcow_seg_plan_stats(self.h.data_ptr(), self.used, C.byref(s)), "gcow_seg_plan_stats")
+        return s
+
+    def segment(self, s: int):
+        """-> (vb0, off, n) of tensor s (an empty tensor: those of the next non-empty one, n 0)."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.L.gcow_seg_plan_segment(self.h.data_ptr(), self.used, s, C.byref(a), C.byref(b), C.byref(c)),
+              "gcow_seg_plan_segment")
+        return a.value, b.value, c.value
+
+    def tile(self, t: int):
+        """-> (the tensor of tile t's first block, whether the tile is whole blocks of that tensor alone)."""
+        a, u = C.c_uint64(0), C.c_int(0)
+        check(self.L.gcow_seg_plan_tile(self.h.data_ptr(), self.used, t, C.byref(a), C.byref(u)), "gcow_seg_plan_tile")
+        return a.value, bool(u.value)
+
+    def max_output_bytes(self) -> int:
+        return self.L.gcow_encode_seg_max_output_bytes(self.h.data_ptr(), self.used)
+
+    def workspace_bytes(self) -> int:
+        return self.L.gcow_encode_seg_workspace_bytes(self.h.data_ptr(), self.used)
+
+    def index_entries(self, index_stride: int) -> int:
+        return self.L.gcow_encode_seg_index_entries(self.h.data_ptr(), self.used, index_stride)
+
+
+def _device_of(device) -> torch.device:
+    """torch.device(device) with the current device's index for a bare "cuda" (tensors report theirs with one)."""
+    device = torch.device(device or "cuda")
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _seg_plan(plan, counts, dtype, device, what):
+    if plan is None:
+        return SegmentPlan(counts, dtype, device)
+    if not isinstance(plan, SegmentPlan) or plan.counts != tuple(int(c) for c in counts) or plan.dtype != dtype:
+        raise GcowError("%s: the plan was made for other counts or another dtype" % what)
+    return plan.to(device)
+
+
+class SegmentedEncoder:
+    """Preallocated segmented encoder (gcow_encode_seg_device) for buffers of one shape: plan, stream, bit count, index
+    and workspace. Calling it with x (contiguous 1-D device tensor of sum(counts) values) and the per-tensor minexp
+    words on x's device (int32[S] packed words, or int64[S, 2] gcow_fit records) launches the encode and returns an
+    Encoded whose `params` is None. The stream is the tensors' streams under expert(1, 16658, maxprec,
+    clamp(minexp_s, -154, 133)) concatenated bit by bit, what a chain of S encode_append calls leaves; with
+    index_stride, index[j] is the bit position of virtual block j * index_stride. Nothing is allocated or read back."""
+
+    def __init__(self, counts, dtype, maxprec: int = 64, device=None, index_stride: int = 0,
+                 plan: SegmentPlan | None = None):
+        self.device = _device_of(device)
+        self.plan = _seg_plan(plan, counts, dtype, self.device, "SegmentedEncoder")
+        self.L = self.plan.L
+        self.maxprec, self.index_stride = int(maxprec), int(index_stride)
+        self.cap = self.plan.max_output_bytes()
+        self.words = torch.zeros(max((self.cap + 7) // 8, 1), dtype=torch.int64, device=self.device)
+        self.bits_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.ws_bytes = self.plan.workspace_bytes()
+        self.ws = torch.zeros(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
+        ne = self.plan.index_entries(index_stride) if index_stride else 0
+        self.index = torch.zeros(max(ne, 1), dtype=torch.int64, device=self.device) if index_stride else None
+
+    def __call__(self, x: torch.Tensor, minexp: torch.Tensor, stream=None) -> Encoded:
+        pl = self.plan
+        if x.dim() != 1 or x.numel() != pl.n or x.dtype != pl.dtype:
+            raise GcowError("segmented encoder built for %d values of %s, got %s %s" % (pl.n, pl.dtype, tuple(x.shape),
+                                                                                       x.dtype))
+        if not (x.is_cuda and x.is_contiguous() and x.device == self.device):
+            raise GcowError("encode_segmented expects a contiguous 1-D tensor on the encoder's device")
+        ns = len(pl.counts)
+        ptr, stride = _fit_records(minexp, ns, x.device, "encode_segmented")
+        check(self.L.gcow_encode_seg_device(pl.h.data_ptr(), pl.d.data_ptr(), pl.used, x.data_ptr() if pl.n else None,
+                                            self.maxprec, ptr if ns else None, stride, self.words.data_ptr(),
+                                            self.words.numel() * 8, self.bits_dev.data_ptr(), self.ws.data_ptr(),
+                                            self.ws.numel() * 8,
+                                            self.index.data_ptr() if self.index is not None else None,
+                                            self.index_stride, _stream_ptr(stream)), "gcow_encode_seg_device")
+        return Encoded(self.words, self.bits_dev, (pl.n,), None, self.index, self.index_stride)
+
+
+def encode_segmented(x: torch.Tensor, counts, minexp: torch.Tensor, maxprec: int = 64, index_stride: int = 0,
+                     stream=None, plan: SegmentPlan | None = None) -> Encoded:
+    """One call of a new SegmentedEncoder (which see); plan: a SegmentPlan of these counts and x's dtype kept by the
+    caller."""
+    return SegmentedEncoder(counts, x.dtype, maxprec, x.device, index_stride, plan)(x, minexp, stream)
+
+
+def decode_mean_segmented(streams: torch.Tensor, stream_words: int, nstreams: int, counts, minexp: torch.Tensor,
+                          maxprec: int = 64, index: torch.Tensor | None = None, index_words: int = 0,
+                          index_stride: int = 16, dtype=torch.float32, out: torch.Tensor | None = None, stream=None,
+                          plan: SegmentPlan | None = None) -> torch.Tensor:
+    """Mean of the decodes of nstreams segmented streams of one shape (gcow_decode_mean_seg_device): stream r at
+    streams[r * stream_words:] (2 readable words after the last one), its index (stride 8 or 16, relative to its first
+    word) at index[r * index_words:]. minexp on the streams' device: one set for all streams -- int32[S] or gcow_fit
+    records int64[S, 2] -- or a set per stream, int32[W, S] or int64[W, S, 2]. Tensor s of `out` (default: new, of
+    `dtype`; fp32 or bf16, contiguous, sum(counts) values) receives what decode_mean gives for its n_s values under its
+    words, accumulated in fp32 in rank order; bf16 rounds to nearest even in the store. One launch."""
+    counts = tuple(int(c) for c in counts)
+    n, ns = sum(counts), len(counts)
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=streams.device)
+    if not (out.is_cuda and out.is_contiguous() and out.numel() == n and out.dtype in (torch.float32, torch.bfloat16)):
+        raise GcowError("decode_mean_segmented: out must be a contiguous fp32 / bf16 device tensor of %d values" % n)
+    pl = plan.to(out.device) if plan is not None and plan.counts == counts else SegmentPlan(counts, out.dtype, out.device)
+    if not (isinstance(minexp, torch.Tensor) and minexp.is_cuda and minexp.is_contiguous()
+            and minexp.dtype in (torch.int32, torch.int64)):
+        raise GcowError("decode_mean_segmented: minexp must be a contiguous int32 / int64 device tensor")
+    per = 1 if minexp.dtype == torch.int32 else 4  # words per tensor
+    have = minexp.numel() * (1 if minexp.dtype == torch.int32 else 2)
+    if have == ns * per:
+        sstride = 0
+    elif have == nstreams * ns * per:
+        sstride = ns * per
+    else:
+        raise GcowError("decode_mean_segmented: minexp must hold one set of %d tensors, or one per stream" % ns)
+    check(pl.L.gcow_decode_mean_seg_device(pl.h.data_ptr(), pl.d.data_ptr(), pl.used, int(maxprec),
+                                           minexp.data_ptr() if ns else None, per, sstride, streams.data_ptr(),
+                                           streams.numel() * 8, stream_words, nstreams,
+                                           index.data_ptr() if index is not None else None, index_words, index_stride,
+                                           out.data_ptr() if n else None,
+                                           DTYPE_BF16 if out.dtype == torch.bfloat16 else DTYPE_FLOAT,
+                                           _stream_ptr(stream)), "gcow_decode_mean_seg_device")
+    return out
+
+
+class PerTensorFittedEncoder:
+    """A bit budget per tensor on the wire, with no host read: calling it with a bucket x (contiguous 1-D device
+    tensor) and the counts of its tensors launches the per-tensor rate tables over the bucket's views
+    (TensorListFittedPerTensor.rate_tables), the batch fit of every table against floor(bits_per_value * n_s) bits over
+    minexp >= minexp_floor, and the segmented encode under the fit records. -> (Encoded, fits): fits is the int64[S, 2]
+    tensor of gcow_fit records (`minexp` is word 0: what a receiver needs to decode), and the stream is at most
+    sum_s floor(bits_per_value * n_s) bits whenever every status is 0. Buffers are made at the first call for a shape
+    (and a bucket address); later calls allocate nothing and synchronise nothing, so the chain captures into one graph
+    that follows the data it is replayed on."""
+
+    def __init__(self, bits_per_value: float, maxprec: int = 64, minexp_floor: int = MINEXP_FLOOR):
+        self.bits_per_value, self.maxprec, self.minexp_floor = float(bits_per_value), int(maxprec), int(minexp_floor)
+        self.lst = TensorListFittedPerTensor(bits_per_value, maxprec, minexp_floor)
+        self.enc = None
+        self._key = None
+
+    @property
+    def fits(self):
+        return self.lst.fits
+
+    def __call__(self, x: torch.Tensor, counts, index_stride: int = 0, stream=None):
+        counts = tuple(int(c) for c in counts)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1 and x.is_contiguous()
+                and x.numel() == sum(counts)):
+            raise GcowError("PerTensorFittedEncoder expects a contiguous 1-D device tensor of sum(counts) values")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device)
+        key = (counts, x.dtype, x.device, int(index_stride))
+        if key != self._key:
+            self.enc = SegmentedEncoder(counts, x.dtype, self.maxprec, x.device, index_stride)
+            self._key = key
+        views = list(torch.split(x, list(counts))) if counts else []
+        lst = self.lst
+        lst.rate_tables(views, stream)
+        if counts:
+            fit_device_batch(lst.tables, lst.budgets, self.minexp_floor, lst.fits, stream)
+        fits = lst.fits if counts else torch.zeros((0, FIT_WORDS), dtype=torch.int64, device=x.device)
+        return self.enc(x, fits, stream), fits
+
+
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):
     """OR src_bits bits of src into dst at dst_bit_offset (device words; dst zeroed beyond earlier content)."""
     L = load()

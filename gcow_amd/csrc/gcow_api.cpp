@@ -1657,6 +1657,237 @@ gcow_status gcow_roundtrip_rel_fitted_device(const void* h_plan, const void* d_p
   return GCOW_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- segmented fields
+static const size_t kSegHeaderBytes = sizeof(gcow::SegHeader);
+
+size_t gcow_seg_plan_bytes(size_t nsegs, uint64_t total_values)
+{
+  // a tensor's blocks are its own: at most total / 4 + nsegs of them; one entry per tensor and the sentinel
+  const uint64_t nvb = total_values / 4 + nsegs;
+  const uint64_t ntiles = (nvb + gcow::kSegTileBlocks - 1) / gcow::kSegTileBlocks;
+  return kSegHeaderBytes + (nsegs + 1) * sizeof(gcow::SegEnt) + (size_t)((ntiles * 4 + 7) / 8 * 8);
+}
+
+gcow_status gcow_seg_plan(const uint64_t* counts, size_t nsegs, data_type dtype, void* h_plan, size_t plan_bytes,
+                          size_t* used_bytes)
+{
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan buffer");
+  if (nsegs && !counts) return fail(GCOW_ERR_INVALID, "null count array");
+  if (dtype != dtype_float && dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "segmented fields are dtype_float or dtype_bf16");
+  if (nsegs >= (1ull << 31)) return fail(GCOW_ERR_UNSUPPORTED, "2^31 tensors or more per call");
+  uint64_t nvals = 0, nvb = 0;
+  std::vector<gcow::SegEnt> ents;
+  for (size_t s = 0; s < nsegs; s++) {
+    const uint64_t n = counts[s];
+    if (!n) continue;
+    if (n >= (1ull << 34) || nvb + (n + 3) / 4 >= (1ull << 32))
+      return fail(GCOW_ERR_UNSUPPORTED, "2^32 virtual blocks or more per call");
+    ents.push_back({nvals, (uint32_t)nvb, (uint32_t)s});
+    nvals += n;
+    nvb += (n + 3) / 4;
+  }
+  if (plan_bytes < gcow_seg_plan_bytes(ents.size(), nvals))
+    return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_seg_plan_bytes()");
+  if ((uintptr_t)h_plan % 8) return fail(GCOW_ERR_INVALID, "misaligned plan buffer");
+  const size_t nlive = ents.size();
+  ents.push_back({nvals, (uint32_t)nvb, (uint32_t)nsegs});  // the sentinel
+  const uint64_t TB = gcow::kSegTileBlocks;
+  const uint64_t ntiles = (nvb + TB - 1) / TB;
+  std::vector<uint32_t> tiles((size_t)ntiles);
+  size_t li = 0;
+  uint32_t nuniform = 0;
+  for (uint64_t t = 0; t < ntiles; t++) {
+    const uint64_t v0 = t * TB, v1 = std::min(v0 + TB, nvb);  // the tile's blocks [v0, v1)
+    while (ents[li + 1].vb0 <= v0) li++;
+    // uniform: the tile ends inside this tensor's whole blocks
+    const uint64_t nfull = (ents[li + 1].off - ents[li].off) / 4;
+    const bool uniform = v1 <= ents[li].vb0 + nfull;
+    nuniform += uniform;
+    tiles[(size_t)t] = (uint32_t)li | (uniform ? 0x80000000u : 0u);
+  }
+  gcow::SegHeader H;
+  std::memset(&H, 0, sizeof(H));
+  H.magic = gcow::kSegMagic;
+  H.dtype = dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32;
+  H.nsegs = (uint32_t)nsegs;
+  H.nlive = (uint32_t)nlive;
+  H.nvals = nvals;
+  H.nvb = nvb;
+  H.ntiles = (uint32_t)ntiles;
+  H.nuniform = nuniform;
+  H.off_ents = kSegHeaderBytes;
+  H.off_tiles = H.off_ents + ents.size() * sizeof(gcow::SegEnt);
+  H.bytes = H.off_tiles + (ntiles * 4 + 7) / 8 * 8;
+  if (H.bytes > plan_bytes) return fail(GCOW_ERR_INVALID, "plan buffer smaller than gcow_seg_plan_bytes()");
+  char* base = (char*)h_plan;
+  std::memset(base, 0, (size_t)H.bytes);
+  std::memcpy(base, &H, sizeof(H));
+  std::memcpy(base + H.off_ents, ents.data(), ents.size() * sizeof(gcow::SegEnt));
+  if (ntiles) std::memcpy(base + H.off_tiles, tiles.data(), (size_t)ntiles * 4);
+  if (used_bytes) *used_bytes = (size_t)H.bytes;
+  return GCOW_OK;
+}
+
+// The header of a host plan, checked against the buffer's size
+static gcow_status seg_header(const void* h_plan, size_t plan_bytes, gcow::SegHeader& H)
+{
+  if (!h_plan) return fail(GCOW_ERR_INVALID, "null plan");
+  if (plan_bytes < sizeof(H)) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  std::memcpy(&H, h_plan, sizeof(H));
+  if (H.magic != gcow::kSegMagic) return fail(GCOW_ERR_INVALID, "not a plan of gcow_seg_plan");
+  if (plan_bytes < H.bytes) return fail(GCOW_ERR_INVALID, "plan_bytes smaller than the plan");
+  return GCOW_OK;
+}
+
+gcow_status gcow_seg_plan_stats(const void* h_plan, size_t plan_bytes, gcow_seg_stats* stats)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!stats) return fail(GCOW_ERR_INVALID, "null stats");
+  stats->total_values = H.nvals;
+  stats->virtual_blocks = H.nvb;
+  stats->segments = H.nlive;
+  stats->tiles = H.ntiles;
+  stats->uniform_tiles = H.nuniform;
+  stats->used_bytes = H.bytes;
+  return GCOW_OK;
+}
+
+static gcow::SegEnt seg_ent(const void* h_plan, const gcow::SegHeader& H, uint64_t i)
+{
+  gcow::SegEnt e;
+  std::memcpy(&e, (const char*)h_plan + H.off_ents + i * sizeof(e), sizeof(e));
+  return e;
+}
+
+gcow_status gcow_seg_plan_segment(const void* h_plan, size_t plan_bytes, uint64_t s, uint64_t* vb0, uint64_t* off,
+                                  uint64_t* n)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!vb0 || !off || !n) return fail(GCOW_ERR_INVALID, "null result pointer");
+  if (s >= H.nsegs) return fail(GCOW_ERR_INVALID, "tensor index out of range");
+  uint64_t lo = 0, hi = H.nlive;  // the first entry (the sentinel included) whose tensor is s or later
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (seg_ent(h_plan, H, mid).seg < s) lo = mid + 1;
+    else hi = mid;
+  }
+  const gcow::SegEnt e = seg_ent(h_plan, H, lo);
+  *vb0 = e.vb0, *off = e.off;
+  *n = e.seg == s ? seg_ent(h_plan, H, lo + 1).off - e.off : 0;
+  return GCOW_OK;
+}
+
+gcow_status gcow_seg_plan_tile(const void* h_plan, size_t plan_bytes, uint64_t t, uint64_t* tensor, int* uniform)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (!tensor || !uniform) return fail(GCOW_ERR_INVALID, "null result pointer");
+  if (t >= H.ntiles) return fail(GCOW_ERR_INVALID, "tile index out of range");
+  uint32_t w;
+  std::memcpy(&w, (const char*)h_plan + H.off_tiles + t * 4, 4);
+  *tensor = seg_ent(h_plan, H, w & 0x7fffffffu).seg;
+  *uniform = (int)(w >> 31);
+  return GCOW_OK;
+}
+
+size_t gcow_encode_seg_max_output_bytes(const void* h_plan, size_t plan_bytes)
+{
+  gcow::SegHeader H;
+  if (seg_header(h_plan, plan_bytes, H)) return 0;
+  return (size_t)((H.nvb * 140 + 63) / 64 * 8 + 8);  // 140: the longest 1-D block (gcow_max_output_bytes' bound)
+}
+
+size_t gcow_encode_seg_workspace_bytes(const void* h_plan, size_t plan_bytes)
+{
+  gcow::SegHeader H;
+  if (seg_header(h_plan, plan_bytes, H)) return 0;
+  return gcow::seg1d_workspace_bytes(H.nvb);
+}
+
+size_t gcow_encode_seg_index_entries(const void* h_plan, size_t plan_bytes, uint32_t index_stride)
+{
+  gcow::SegHeader H;
+  if (!index_stride || seg_header(h_plan, plan_bytes, H)) return 0;
+  return (size_t)((H.nvb + index_stride - 1) / index_stride);
+}
+
+gcow_status gcow_encode_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                   uint32_t maxprec, const int32_t* d_minexp, uint32_t minexp_stride, void* d_out,
+                                   size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                   size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride, void* hip_stream)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!minexp_stride) return fail(GCOW_ERR_INVALID, "a stride of 0 words");
+  if ((uintptr_t)d_total_bits % 8 || (uintptr_t)d_index % 8 || (uintptr_t)d_workspace % 8 || (uintptr_t)d_out % 8)
+    return fail(GCOW_ERR_INVALID, "misaligned output, d_total_bits, d_index or workspace");
+  uint32_t shift = 0;
+  if (d_index) {
+    if (!index_stride || index_stride > 256 || (index_stride & (index_stride - 1)))
+      return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+    while ((1u << shift) < index_stride) shift++;
+  }
+  if (H.nvb) {
+    if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+    if (!d_in || (uintptr_t)d_in % (H.dtype == gcow::DT_BF16 ? 2 : 4))
+      return fail(GCOW_ERR_INVALID, "null input, or misaligned for its element type");
+    if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+    if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+    if (out_capacity < gcow_encode_seg_max_output_bytes(h_plan, plan_bytes))
+      return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_encode_seg_max_output_bytes()");
+    if (!d_workspace || workspace_bytes < gcow::seg1d_workspace_bytes(H.nvb))
+      return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_seg_workspace_bytes()");
+  } else if (!d_total_bits) {
+    return GCOW_OK;  // an empty list and no bit count: nothing to write
+  }
+  GCOW_HIP(gcow::launch_encode_seg1d(H, d_plan, d_in, maxprec, d_minexp, minexp_stride, (uint32_t*)d_out,
+                                     (uint64_t*)d_workspace, d_total_bits, d_index, shift, hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_decode_mean_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                        const int32_t* d_minexp, uint32_t minexp_stride, uint64_t minexp_stream_stride,
+                                        const uint64_t* d_streams, size_t streams_bytes, uint64_t stream_words,
+                                        uint32_t nstreams, const uint64_t* d_index, uint64_t index_words,
+                                        uint32_t index_stride, void* d_out, data_type out_dtype, void* hip_stream)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (out_dtype != dtype_float && out_dtype != dtype_bf16)
+    return fail(GCOW_ERR_UNSUPPORTED, "decode_mean_seg writes dtype_float or dtype_bf16");
+  if (!minexp_stride) return fail(GCOW_ERR_INVALID, "a stride of 0 words");
+  if (index_stride != 8 && index_stride != 16)
+    return fail(GCOW_ERR_INVALID, "decode_mean_seg needs each stream's index at stride 8 or 16");
+  if (!nstreams) return fail(GCOW_ERR_INVALID, "no streams");
+  if (!H.nvb) return GCOW_OK;
+  if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+  if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+  if (!d_streams || (uintptr_t)d_streams % 8) return fail(GCOW_ERR_INVALID, "null or misaligned streams");
+  // the decoders read up to two words past a stream's last bit (64-bit windows): the buffer holds them
+  if (streams_bytes / 8 < (uint64_t)nstreams * stream_words + 2)
+    return fail(GCOW_ERR_INVALID, "stream buffer smaller than nstreams * stream_words + 2 words");
+  if (!d_index || (uintptr_t)d_index % 8 || index_words < (H.nvb + index_stride - 1) / index_stride)
+    return fail(GCOW_ERR_INVALID, "null, misaligned or short block index");
+  if (!d_out || (uintptr_t)d_out % (out_dtype == dtype_bf16 ? 2 : 4))
+    return fail(GCOW_ERR_INVALID, "null output, or misaligned for its element type");
+  GCOW_HIP(gcow::launch_decode_mean_seg1d(H, d_plan, maxprec, d_minexp, minexp_stride, minexp_stream_stride, d_streams,
+                                          stream_words, nstreams, d_index, index_words, index_stride, d_out,
+                                          out_dtype == dtype_bf16 ? gcow::DT_BF16 : gcow::DT_F32, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

@@ -267,6 +267,36 @@ hipError_t launch_roundtrip_list1d_fitted(const RtListHeader& h, const void* d_p
 // pass). total (optional): set to the sum of every block's bit length.
 hipError_t launch_roundtrip_rel1d_fitted(const RtRelHeader& h, const void* d_plan, uint32_t maxprec,
                                          const int32_t* d_minexp, uint32_t stride_words, uint64_t* total, void* stream);
+// The segmented 1-D codec (seg1d.hip; include/gcow.h "Segmented fields"). The plan (gcow_seg_plan, gcow_api.cpp) is one
+// buffer without pointers: SegHeader, then nlive + 1 SegEnt -- the non-empty tensors in list order and a sentinel
+// {nvals, nvb, nsegs} -- and ntiles words, one per tile of kSegTileBlocks virtual blocks: the entry of the tensor that
+// holds the tile's first block, and bit 31 set when every block of the tile is a whole block of that tensor.
+constexpr uint32_t kSegMagic = 0x4c475367u;  // "gSGL"
+constexpr uint32_t kSegTileBlocks = 1024;
+struct SegEnt {
+  uint64_t off;  // the tensor's first value in the buffer
+  uint32_t vb0;  // its first virtual block
+  uint32_t seg;  // its number in the caller's list
+};
+struct SegHeader {
+  uint32_t magic, dtype, nsegs, nlive;
+  uint64_t nvals, nvb;  // values, virtual blocks
+  uint32_t ntiles, nuniform;
+  uint64_t off_ents, off_tiles, bytes;  // byte offsets into the plan; bytes = the plan's used size
+};
+static_assert(sizeof(SegEnt) == 16 && sizeof(SegHeader) == 64, "plan layout");
+// ws = seg1d_workspace_bytes(nvb), the V1Workspace layout; stream, *d_total, index as launch_encode1d_var_tile writes
+// them for one field of nvb blocks (no d_base); tensor s under clamp(d_minexp[s * stride_words], -154, 133).
+size_t seg1d_workspace_bytes(uint64_t nvb);
+hipError_t launch_encode_seg1d(const SegHeader& H, const void* d_plan, const void* in, uint32_t maxprec,
+                               const int32_t* d_minexp, uint32_t stride_words, uint32_t* out32, uint64_t* ws,
+                               uint64_t* d_total, uint64_t* index, uint32_t index_shift, void* stream);
+// mean of nstreams segmented streams (index every chunk = 8 or 16 virtual blocks, index_words entries apart); stream r
+// reads its words at d_minexp[r * stream_stride_words + s * stride_words]; out: the buffer's first value.
+hipError_t launch_decode_mean_seg1d(const SegHeader& H, const void* d_plan, uint32_t maxprec, const int32_t* d_minexp,
+                                    uint32_t stride_words, uint64_t stream_stride_words, const uint64_t* in,
+                                    uint64_t stream_words, uint32_t nstreams, const uint64_t* index,
+                                    uint64_t index_words, uint32_t chunk, void* out, int out_dtype, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

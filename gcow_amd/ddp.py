@@ -146,9 +146,13 @@ class GcowHookState:
     whatever `fit_on_device` says -- and `fit_record(index)` is the int64[S, 2] tensor of the bucket's records. A quiet
     layer keeps its own tolerance and a loud one cannot take its bits; fits stop at minexp -94 (include/gcow.h).
     `params` supplies maxprec. The bucket must be fp32 or bf16. ValueError: without `target_bits`; with
-    `relative_bits` (both choose the tolerance), `error_feedback` or `compress_mean`; registered with a wire hook,
-    whose decoder would need the per-tensor minexp on the wire; a codec without roundtrip_fitted_per_tensor. Unset
-    (the default): nothing changes."""
+    `relative_bits` (both choose the tolerance), `error_feedback` or `compress_mean`; registered with
+    compressed_sharded_hook, whose pieces carry no per-tensor minexp; a codec without roundtrip_fitted_per_tensor.
+    compressed_allgather_hook takes it too (with `target_bits`; _allgather_per_tensor): each rank fits its own
+    gradients, sends one segmented stream (a minexp per tensor, read on the device) and its S fit records, 16 bytes
+    per tensor, and every rank decodes and averages the W streams under the W sets in one launch. The bucket's
+    gradients must tile its flat buffer in order; a codec without encode_per_tensor / decode_mean_per_tensor, and
+    `error_feedback`: ValueError. Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -378,8 +382,9 @@ def _fit_next(state: GcowHookState, table: torch.Tensor, index, n: int, world: i
     state._fits[index] = (n, me)
 
 
-_PER_TENSOR_WIRE = ("per_tensor_budget is for roundtrip_hook: a stream coded under a minexp per tensor needs them on "
-                    "the wire to be decoded, which the wire hooks do not send")
+_PER_TENSOR_WIRE = ("per_tensor_budget is for roundtrip_hook and compressed_allgather_hook: a stream coded under a "
+                    "minexp per tensor needs them on the wire to be decoded, which only the all-gather hook's segmented "
+                    "exchange sends")
 _RELATIVE_WIRE = ("relative_bits is for roundtrip_hook: a stream coded under per-tensor exponents needs them on the "
                   "wire to be decoded, which the wire hooks do not send")
 
@@ -505,6 +510,95 @@ class _CommWorker:
         return fut
 
 
+def _bucket_counts(bucket, buf: torch.Tensor):
+    """The sizes of the bucket's gradients when they tile its flat buffer in order (pointer arithmetic), else
+    ValueError: the segmented stream is cut where the gradients lie."""
+    grads = list(bucket.gradients())
+    at, esz = buf.data_ptr(), buf.element_size()
+    counts = []
+    for g in grads:
+        n = g.numel()
+        if g.dtype != buf.dtype or (n and (not g.is_contiguous() or g.data_ptr() != at)):
+            raise ValueError("per_tensor_budget on the wire: the bucket's gradients must tile its flat buffer in "
+                             "order (gradient %d does not lie where the one before it ends)" % len(counts))
+        counts.append(n)
+        at += n * esz
+    if sum(counts) != buf.numel():
+        raise ValueError("per_tensor_budget on the wire: the bucket's gradients cover %d of its %d values"
+                         % (sum(counts), buf.numel()))
+    return counts
+
+
+def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
+    """compressed_allgather_hook with per_tensor_budget: every rank fits its own gradients -- per-tensor rate tables,
+    one batch fit against floor(target_bits * n_s) bits, the segmented encode under the records, with a 16-block index,
+    launched on the autograd thread with nothing read back -- so its stream is at most sum_s floor(target_bits * n_s)
+    bits whenever every record's status is 0. On the comm thread: the gathered lengths (the one host read), the padded
+    all-gather of the words, the all-gather of the index, and the all-gather of each rank's S fit records, 16 bytes per
+    tensor: that is the wire format of the per-tensor minexp (word 0 of a record). Then one decode-mean straight into
+    the bucket, stream r's tensor s under record (r, s). No table is all-reduced and no minexp reaches the host;
+    state.fit_record(index) is this rank's int64[S, 2] records."""
+    if state.error_feedback:
+        raise ValueError("per_tensor_budget on the wire has no residual form: error_feedback cannot be combined with it")
+    state.check_target()
+    cdc = state.get_codec()
+    missing = [m for m in ("encode_per_tensor", "decode_mean_per_tensor") if not hasattr(cdc, m)]
+    if missing:
+        raise ValueError("per_tensor_budget with compressed_allgather_hook needs a codec with %s "
+                         "(gcow_amd.dist.DeviceCodec): %s" % (", ".join(missing), _PER_TENSOR_WIRE))
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError("compressed_allgather_hook with per_tensor_budget needs an initialised process group")
+    group = state.process_group
+    buf = bucket.buffer()
+    if buf.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("per_tensor_budget takes fp32 or bf16 buckets, got %s" % buf.dtype)
+    flat = buf.reshape(-1)
+    if not flat.is_contiguous() or flat.data_ptr() != buf.data_ptr():
+        raise ValueError("per_tensor_budget on the wire takes a contiguous bucket buffer")
+    counts = _bucket_counts(bucket, flat)
+    world = dist.get_world_size(group)
+    slot = bucket.index() if hasattr(bucket, "index") else None
+    maxprec = state.params.maxprec
+    cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
+    words, bits, index, fits = cdc.encode_per_tensor(flat, counts, state.target_bits, maxprec, INDEX_STRIDE,
+                                                     slot=("per_tensor", slot))
+    state._fit_records[slot] = fits
+    dev = flat.device
+    if dev.type == "cuda":
+        ev = torch.cuda.Event()
+        ev.record()
+        side = state.side_stream(dev)
+        fut = torch.futures.Future(devices=[dev])
+    else:
+        ev = side = None
+        fut = torch.futures.Future()
+
+    def exchange(fut):
+        if side is not None:
+            torch.cuda.set_device(dev)
+        ctx = torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
+        with ctx:
+            if side is not None:
+                side.wait_event(ev)
+                for t in (words, bits, index, fits):
+                    t.record_stream(side)
+            lens, lens_h = gdist.gather_lengths(bits, dev, cgroup)  # host read: this thread waits, autograd does not
+            maxw = max(1, max((b + 63) // 64 for b in lens_h))
+            rank = dist.get_rank(cgroup)
+            gathered = gdist.allgather_padded(words, (lens_h[rank] + 63) // 64, maxw, cgroup, pad=2)
+            ni = index.numel()
+            idx = torch.empty(world * ni, dtype=torch.int64, device=dev)
+            gdist.allgather_into(idx, index[:ni].contiguous(), cgroup)
+            mine = fits.reshape(-1).contiguous()  # S records of 16 bytes: minexp | status << 32, bits
+            recs = torch.empty(world * mine.numel(), dtype=torch.int64, device=dev)
+            gdist.allgather_into(recs, mine, cgroup)
+            cdc.decode_mean_per_tensor(gathered, maxw, world, counts, recs, maxprec, idx, ni, INDEX_STRIDE, out=flat,
+                                       slot=("per_tensor", slot))
+            fut.set_result(buf)
+
+    return state.worker().submit(exchange, fut)
+
+
 def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
     """Encode locally, all-gather the compressed streams, decode every rank's stream and average (one launch).
 
@@ -520,7 +614,7 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     if state.relative_bits is not None:
         raise ValueError(_RELATIVE_WIRE)
     if state.per_tensor_budget:
-        raise ValueError(_PER_TENSOR_WIRE)
+        return _allgather_per_tensor(state, bucket)
     state.check_target()
     cdc = state.get_codec()
     fod = state.check_fit_on_device(cdc, "compressed_allgather_hook")  # before any collective

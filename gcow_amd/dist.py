@@ -227,6 +227,32 @@ class DeviceCodec:
         from . import codec
         return codec.roundtrip_fitted(x, minexp_word, maxprec, out=out)
 
+    def encode_per_tensor(self, x: torch.Tensor, counts, bits_per_value: float, maxprec: int = 64,
+                          index_stride: int = 0, slot=None):
+        """The bucket x (contiguous 1-D, its tensors `counts` values each, in order) encoded with a bit budget per
+        tensor, fitted on the device (codec.PerTensorFittedEncoder: per-tensor tables, batch fit, segmented encode; no
+        host read): -> (words, bits, index, fits), fits the int64[S, 2] gcow_fit records a receiver decodes under.
+        Cached per (slot, counts, dtype, device, budget, maxprec, index stride) like the encoders."""
+        from . import codec
+        counts = tuple(int(c) for c in counts)
+        key = (slot, counts, x.dtype, x.device, float(bits_per_value), int(maxprec), index_stride, "per_tensor")
+        enc = self._cached(key, lambda: codec.PerTensorFittedEncoder(bits_per_value, maxprec))
+        e, fits = enc(x, counts, index_stride)
+        return e.words, e.bits_dev, e.index, fits
+
+    def decode_mean_per_tensor(self, streams, stream_words: int, nstreams: int, counts, fits, maxprec: int = 64,
+                               index=None, index_words: int = 0, index_stride: int = 16, out=None, slot=None):
+        """The mean of nstreams segmented streams of one shape, each tensor under its stream's own fit
+        (codec.decode_mean_segmented): fits is one set (int64[S, 2] records or int32[S] words) or one per stream
+        (int64[W, S, 2] / int32[W, S]). The plan is cached per (slot, counts, dtype, device)."""
+        from . import codec
+        counts = tuple(int(c) for c in counts)
+        dtype = out.dtype if out is not None else torch.float32
+        key = (slot, counts, dtype, streams.device, "segment_plan")
+        plan = self._cached(key, lambda: codec.SegmentPlan(counts, dtype, streams.device))
+        return codec.decode_mean_segmented(streams, stream_words, nstreams, counts, fits, maxprec, index, index_words,
+                                           index_stride, dtype, out, plan=plan)
+
     def pack_index16(self, index8, n: int, params):
         from . import codec
         return codec.pack_index16(index8, n, params)

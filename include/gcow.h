@@ -640,6 +640,86 @@ gcow_status gcow_roundtrip_rel_fitted_device(const void* h_plan, const void* d_p
                                              uint64_t* d_total_bits, void* hip_stream);
 
 /*
+ * Segmented fields: a minexp per tensor ON THE WIRE. The calls above choose a tolerance per tensor but leave no
+ * stream; these code one contiguous buffer that holds S tensors back to back into ONE stream, every tensor under its
+ * own minexp, and decode-and-average W such streams, each in a number of launches that does not depend on S.
+ *
+ * A segmented field is
+ *   - a contiguous 1-D DEVICE array of n values, dtype_float or dtype_bf16, at any element-aligned address;
+ *   - a host list counts[S] with sum n (zeros allowed);
+ *   - a DEVICE int32 array of minexp words, one per tensor in the caller's numbering, read at
+ *     d_minexp[s * minexp_stride] ON THE DEVICE when the kernels run: a stride of 1 for packed words, 4 for an array
+ *     of gcow_fit records (minexp is word 0 of a record).
+ * Tensor s is the slice [off_s, off_s + n_s), off_s = sum_{r<s} n_r, and is a field of its own: its blocks are counted
+ * from its first value, its last block is padded as a partial block, no block crosses a tensor. It is coded under
+ * p_s = expert(1, 16658, maxprec, clamp(minexp_s, -154, 133)), the clamp of the fitted calls. Virtual block v counts
+ * the blocks of all tensors in list order: vb0_s = sum_{r<s} ceil(n_r / 4). Empty tensors contribute none and their
+ * word is never read.
+ *
+ * The stream is exactly what results from: start at bit 0; gcow_encode_device_append(field(t_s), p_s) for s = 0 ..
+ * S - 1 in order; flush once to a 64-bit boundary at the end. The tensors' streams are concatenated at bit
+ * granularity, no padding between them. *d_total_bits (optional) is the sum of the tensors' bit counts. With
+ * index_stride (a power of two in [1, 256]; d_index NULL: no index) d_index[j] is the bit position of virtual block
+ * j * index_stride, gcow_encode_seg_index_entries of them. Output, workspace and index need no zeroing by the caller;
+ * nothing is written past the flushed words; an empty list writes *d_total_bits = 0 and nothing else.
+ *
+ * The plan (host; gcow_seg_plan_bytes bounds its size, used_bytes is what to copy to the device): a private layout that
+ * holds no pointers and depends on neither maxprec nor the words, so one plan serves every buffer of that shape, the
+ * encode and the decode. It carries vb0_s and off_s of the non-empty tensors and, per tile of 1024 virtual blocks, the
+ * tensor of the tile's first block and whether every block of the tile is a whole block of that one tensor (a
+ * "uniform" tile): a lane bisects over the tensors of its own tile only. gcow_seg_plan_stats reports the counts;
+ * gcow_seg_plan_segment gives vb0_s / off_s / n_s of tensor s (an empty tensor: those of the next non-empty one, n 0),
+ * gcow_seg_plan_tile the tensor (caller's numbering) of tile t's first block and the uniform flag.
+ * gcow_encode_seg_max_output_bytes / _workspace_bytes / _index_entries: the sizes for a plan (0 for a NULL or foreign
+ * one, index_stride 0: 0 entries).
+ *
+ * gcow_decode_mean_seg_device: for W = nstreams streams of one segmented shape (stream r at d_streams + r *
+ * stream_words, its index -- relative to its own first word -- at d_index + r * index_words, index_stride 8 or 16),
+ * tensor s of d_out receives exactly what gcow_decode_mean_device writes for a 1-D field of n_s values under p_{r,s},
+ * from the W sub-streams at their bit positions: ((0 + x_0) + x_1 + ...) / W in fp32 in rank order; out_dtype
+ * dtype_bf16 rounds to nearest even in the store. Stream r reads its words at d_minexp[r * minexp_stream_stride +
+ * s * minexp_stride]; minexp_stream_stride = 0: one set for all streams. W = 1 is the plain decode. The decoders'
+ * contract holds (below): every slot may hold anything from its stream's last bit on, the two words after the last
+ * slot likewise (streams_bytes covers them), stream_words may be odd. Only real values are written, nothing outside
+ * [d_out, d_out + n). An empty list does nothing.
+ *
+ * Refusals, all on the host before any launch. GCOW_ERR_UNSUPPORTED: 2^32 virtual blocks or more, 2^31 tensors or
+ * more, a dtype other than dtype_float / dtype_bf16. GCOW_ERR_INVALID: a NULL h_plan or counts with nsegs > 0, a
+ * plan buffer below gcow_seg_plan_bytes or misaligned (8 bytes); a NULL, short or foreign plan; with a non-empty list a
+ * NULL or misaligned d_plan (8), d_in / d_out (element), d_minexp (4), d_out stream (8), workspace (8) below its query,
+ * a misaligned d_total_bits / d_index, a minexp_stride of 0, an index_stride that is no power of two in [1, 256]
+ * (decode: not 8 or 16, or a NULL index, or index_words below the entries), no streams, streams_bytes below
+ * nstreams * stream_words + 2 words; maxprec as check_params has it. GCOW_ERR_CAPACITY: out_capacity below the query.
+ */
+typedef struct {
+  uint64_t total_values;
+  uint64_t virtual_blocks;
+  uint64_t segments;       /* non-empty tensors */
+  uint64_t tiles;          /* of 1024 virtual blocks */
+  uint64_t uniform_tiles;
+  uint64_t used_bytes;
+} gcow_seg_stats;
+size_t gcow_seg_plan_bytes(size_t nsegs, uint64_t total_values);
+gcow_status gcow_seg_plan(const uint64_t* counts, size_t nsegs, data_type dtype, void* h_plan, size_t plan_bytes,
+                          size_t* used_bytes);
+gcow_status gcow_seg_plan_stats(const void* h_plan, size_t plan_bytes, gcow_seg_stats* stats);
+gcow_status gcow_seg_plan_segment(const void* h_plan, size_t plan_bytes, uint64_t s, uint64_t* vb0, uint64_t* off,
+                                  uint64_t* n);
+gcow_status gcow_seg_plan_tile(const void* h_plan, size_t plan_bytes, uint64_t t, uint64_t* tensor, int* uniform);
+size_t gcow_encode_seg_max_output_bytes(const void* h_plan, size_t plan_bytes);
+size_t gcow_encode_seg_workspace_bytes(const void* h_plan, size_t plan_bytes);
+size_t gcow_encode_seg_index_entries(const void* h_plan, size_t plan_bytes, uint32_t index_stride);
+gcow_status gcow_encode_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                   uint32_t maxprec, const int32_t* d_minexp, uint32_t minexp_stride, void* d_out,
+                                   size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                   size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride, void* hip_stream);
+gcow_status gcow_decode_mean_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, uint32_t maxprec,
+                                        const int32_t* d_minexp, uint32_t minexp_stride, uint64_t minexp_stream_stride,
+                                        const uint64_t* d_streams, size_t streams_bytes, uint64_t stream_words,
+                                        uint32_t nstreams, const uint64_t* d_index, uint64_t index_words,
+                                        uint32_t index_stride, void* d_out, data_type out_dtype, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by
