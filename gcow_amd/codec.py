@@ -1418,6 +1418,131 @@ class PerTensorFittedEncoder:
         return self.enc(x, fits, stream), fits
 
 
+# ------------------------------------------------------- segmented fields with a residual: error feedback per tensor
+def _check_seg_err(x: torch.Tensor, err, what: str, name: str = "err"):
+    if not (isinstance(err, torch.Tensor) and err.is_cuda and err.device == x.device and err.dtype == torch.float32
+            and err.dim() == 1 and err.numel() == x.numel() and err.is_contiguous()):
+        raise GcowError("%s: %s must be a contiguous 1-D float32 tensor of x's size on x's device" % (what, name))
+
+
+def _check_seg_x(x, pl: SegmentPlan, device, what: str):
+    if not (isinstance(x, torch.Tensor) and x.dim() == 1 and x.numel() == pl.n and x.dtype == pl.dtype):
+        raise GcowError("%s: built for %d values of %s" % (what, pl.n, pl.dtype))
+    if not (x.is_cuda and x.is_contiguous() and x.device == device):
+        raise GcowError("%s expects a contiguous 1-D tensor on the plan's device" % what)
+
+
+class SegmentedRateTables:
+    """Preallocated per-tensor rate tables of a segmented field with a carried error (gcow_rate_table_seg_device) for
+    buffers of one shape: plan, tables (`tables`, int64[S, 288]) and workspace. Calling it with x and err (fp32, parallel
+    to x; None: zeros) launches one pass over the plan's tiles: row s is rate_table_residual(t_s, e_s, maxprec), exactly
+    (zeros for an empty tensor). Nothing is allocated or read back."""
+
+    def __init__(self, counts, dtype, maxprec: int = 64, device=None, plan: SegmentPlan | None = None):
+        self.device = _device_of(device)
+        self.plan = _seg_plan(plan, counts, dtype, self.device, "SegmentedRateTables")
+        self.L = self.plan.L
+        self.maxprec = int(maxprec)
+        ns = len(self.plan.counts)
+        self.ws_bytes = self.L.gcow_rate_table_seg_workspace_bytes(self.plan.h.data_ptr(), self.plan.used)
+        self.ws = torch.empty(max(self.ws_bytes // 8, 1), dtype=torch.int64, device=self.device)
+        self.tables = torch.empty((ns, RATE_TABLE_ENTRIES), dtype=torch.int64, device=self.device)
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        pl = self.plan
+        _check_seg_x(x, pl, self.device, "rate_tables_segmented")
+        if err is not None:
+            _check_seg_err(x, err, "rate_tables_segmented")
+        ns = len(pl.counts)
+        check(self.L.gcow_rate_table_seg_device(pl.h.data_ptr(), pl.d.data_ptr(), pl.used,
+                                                x.data_ptr() if pl.n else None,
+                                                err.data_ptr() if err is not None and pl.n else None, self.maxprec,
+                                                self.tables.data_ptr() if ns else None, self.ws.data_ptr(),
+                                                self.ws.numel() * 8, _stream_ptr(stream)),
+              "gcow_rate_table_seg_device")
+        return self.tables
+
+
+def rate_tables_segmented(x: torch.Tensor, counts, err: torch.Tensor | None = None, maxprec: int = 64,
+                          plan: SegmentPlan | None = None, stream=None) -> torch.Tensor:
+    """The rate table of y = x + err of every tensor of a segmented field from one pass (gcow_rate_table_seg_device):
+    int64[S, 288] on x's device, row s the stream lengths of t_s + e_s under expert(1, 16658, maxprec, minexp),
+    minexp = -154 .. 133, exactly -- what encode_segmented_residual spends on tensor s. err None: zeros, the tables of x
+    (rate_tables_tensors' rows). One call of a new SegmentedRateTables; plan: a SegmentPlan kept by the caller."""
+    return SegmentedRateTables(counts, x.dtype, maxprec, x.device, plan)(x, err, stream)
+
+
+class SegmentedResidualEncoder(SegmentedEncoder):
+    """SegmentedEncoder with error feedback (gcow_encode_seg_residual_device): calling it with x, err (fp32, parallel
+    to x; None: zeros) and the per-tensor minexp words codes y = x + err -- the stream, bit count and index are
+    encode_segmented's for the fp32 tensor y -- and writes e' = y - decode(y) (non-finite: +0) for every tensor under
+    its own word: into err itself by default, into `err_out` when given (err_out is required with err None). x is only
+    read. Nothing is allocated or read back."""
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor | None, minexp: torch.Tensor,
+                 err_out: torch.Tensor | None = None, stream=None) -> Encoded:
+        pl = self.plan
+        what = "encode_segmented_residual"
+        _check_seg_x(x, pl, self.device, what)
+        if err is not None:
+            _check_seg_err(x, err, what)
+        if err_out is None:
+            err_out = err
+        if err_out is None:
+            raise GcowError("%s: err None (zeros) needs err_out" % what)
+        _check_seg_err(x, err_out, what, "err_out")
+        ns = len(pl.counts)
+        ptr, stride = _fit_records(minexp, ns, x.device, what)
+        check(self.L.gcow_encode_seg_residual_device(
+            pl.h.data_ptr(), pl.d.data_ptr(), pl.used, x.data_ptr() if pl.n else None,
+            err.data_ptr() if err is not None and pl.n else None, err_out.data_ptr() if pl.n else None, self.maxprec,
+            ptr if ns else None, stride, self.words.data_ptr(), self.words.numel() * 8, self.bits_dev.data_ptr(),
+            self.ws.data_ptr(), self.ws.numel() * 8, self.index.data_ptr() if self.index is not None else None,
+            self.index_stride, _stream_ptr(stream)), "gcow_encode_seg_residual_device")
+        return Encoded(self.words, self.bits_dev, (pl.n,), None, self.index, self.index_stride)
+
+
+def encode_segmented_residual(x: torch.Tensor, err: torch.Tensor | None, counts, minexp: torch.Tensor,
+                              maxprec: int = 64, index_stride: int = 0, err_out: torch.Tensor | None = None,
+                              stream=None, plan: SegmentPlan | None = None) -> Encoded:
+    """One call of a new SegmentedResidualEncoder (which see): err is updated in place unless err_out is given."""
+    return SegmentedResidualEncoder(counts, x.dtype, maxprec, x.device, index_stride, plan)(x, err, minexp, err_out,
+                                                                                            stream)
+
+
+class PerTensorFittedResidualEncoder:
+    """PerTensorFittedEncoder with error feedback: calling it with a bucket x, the carried error err (fp32, parallel to
+    x, updated in place), the counts and an index stride launches the per-tensor rate tables of y = x + err
+    (SegmentedRateTables), the batch fit of every table against floor(bits_per_value * n_s) bits over minexp >=
+    minexp_floor, and the segmented residual encode under the fit records. -> (Encoded, fits) as PerTensorFittedEncoder.
+    One SegmentPlan serves the tables and the encode. Buffers are made and the budgets uploaded at the first call for
+    a shape; later calls allocate nothing and read nothing back, so the chain captures into one graph."""
+
+    def __init__(self, bits_per_value: float, maxprec: int = 64, minexp_floor: int = MINEXP_FLOOR):
+        self.bits_per_value, self.maxprec, self.minexp_floor = float(bits_per_value), int(maxprec), int(minexp_floor)
+        self.enc = self.tab = self.fits = self.budgets = None
+        self._key = None
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor, counts, index_stride: int = 0, stream=None):
+        counts = tuple(int(c) for c in counts)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1 and x.is_contiguous()
+                and x.numel() == sum(counts)):
+            raise GcowError("PerTensorFittedResidualEncoder expects a contiguous 1-D device tensor of sum(counts) values")
+        key = (counts, x.dtype, x.device, int(index_stride))
+        if key != self._key:
+            self.enc = SegmentedResidualEncoder(counts, x.dtype, self.maxprec, x.device, index_stride)
+            self.tab = SegmentedRateTables(counts, x.dtype, self.maxprec, x.device, self.enc.plan)
+            ns = len(counts)
+            self.fits = torch.zeros((ns, FIT_WORDS), dtype=torch.int64, device=x.device)
+            self.budgets = torch.tensor([int(math.floor(self.bits_per_value * c)) for c in counts],
+                                        dtype=torch.int64).to(x.device)
+            self._key = key
+        tables = self.tab(x, err, stream)
+        if counts:
+            fit_device_batch(tables, self.budgets, self.minexp_floor, self.fits, stream)
+        return self.enc(x, err, self.fits, None, stream), self.fits
+
+
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):
     """OR src_bits bits of src into dst at dst_bit_offset (device words; dst zeroed beyond earlier content)."""
     L = load()

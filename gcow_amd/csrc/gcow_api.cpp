@@ -1888,6 +1888,80 @@ gcow_status gcow_decode_mean_seg_device(const void* h_plan, const void* d_plan, 
   return GCOW_OK;
 }
 
+// ------------------------------------------------------------------------------- segmented fields with a residual
+size_t gcow_rate_table_seg_workspace_bytes(const void* h_plan, size_t plan_bytes)
+{
+  gcow::SegHeader H;
+  if (seg_header(h_plan, plan_bytes, H)) return 0;
+  return gcow::rate_table_rel_workspace_bytes(H.nsegs);  // a function of nsegs only
+}
+
+gcow_status gcow_rate_table_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                       const float* d_err_in, uint32_t maxprec, uint64_t* d_tables, void* d_workspace,
+                                       size_t workspace_bytes, void* hip_stream)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if ((uintptr_t)d_err_in % 4) return fail(GCOW_ERR_INVALID, "misaligned d_err_in");
+  if (!H.nsegs) return GCOW_OK;  // no tensor: no row
+  if (!d_tables || (uintptr_t)d_tables % 8) return fail(GCOW_ERR_INVALID, "null or misaligned tables");
+  if (!d_workspace || (uintptr_t)d_workspace % 8 || workspace_bytes < gcow::rate_table_rel_workspace_bytes(H.nsegs))
+    return fail(GCOW_ERR_INVALID, "workspace null, misaligned or smaller than gcow_rate_table_seg_workspace_bytes()");
+  if (H.nvb) {
+    if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+    if (!d_in || (uintptr_t)d_in % (H.dtype == gcow::DT_BF16 ? 2 : 4))
+      return fail(GCOW_ERR_INVALID, "null input, or misaligned for its element type");
+  }
+  GCOW_HIP(gcow::launch_rate_table_seg1d(H, d_plan, d_in, d_err_in, maxprec, d_tables, (uint64_t*)d_workspace,
+                                         hip_stream));
+  return GCOW_OK;
+}
+
+gcow_status gcow_encode_seg_residual_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                            const float* d_err_in, float* d_err_out, uint32_t maxprec,
+                                            const int32_t* d_minexp, uint32_t minexp_stride, void* d_out,
+                                            size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                            size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                            void* hip_stream)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  const gcow_params hp = fitted_host_params(maxprec);
+  if ((st = check_params(&hp, 1))) return st;
+  if (!minexp_stride) return fail(GCOW_ERR_INVALID, "a stride of 0 words");
+  if ((uintptr_t)d_total_bits % 8 || (uintptr_t)d_index % 8 || (uintptr_t)d_workspace % 8 || (uintptr_t)d_out % 8)
+    return fail(GCOW_ERR_INVALID, "misaligned output, d_total_bits, d_index or workspace");
+  if ((uintptr_t)d_err_in % 4 || (uintptr_t)d_err_out % 4) return fail(GCOW_ERR_INVALID, "misaligned d_err_in or d_err_out");
+  uint32_t shift = 0;
+  if (d_index) {
+    if (!index_stride || index_stride > 256 || (index_stride & (index_stride - 1)))
+      return fail(GCOW_ERR_INVALID, "index_stride must be a power of two in [1, 256]");
+    while ((1u << shift) < index_stride) shift++;
+  }
+  if (H.nvb) {
+    if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+    if (!d_in || (uintptr_t)d_in % (H.dtype == gcow::DT_BF16 ? 2 : 4))
+      return fail(GCOW_ERR_INVALID, "null input, or misaligned for its element type");
+    if (!d_err_out) return fail(GCOW_ERR_INVALID, "null d_err_out");
+    if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+    if (!d_out) return fail(GCOW_ERR_INVALID, "null output");
+    if (out_capacity < gcow_encode_seg_max_output_bytes(h_plan, plan_bytes))
+      return fail(GCOW_ERR_CAPACITY, "output capacity below gcow_encode_seg_max_output_bytes()");
+    if (!d_workspace || workspace_bytes < gcow::seg1d_workspace_bytes(H.nvb))
+      return fail(GCOW_ERR_INVALID, "workspace smaller than gcow_encode_seg_workspace_bytes()");
+  } else if (!d_total_bits) {
+    return GCOW_OK;  // an empty list and no bit count: nothing to write
+  }
+  GCOW_HIP(gcow::launch_encode_seg_resid1d(H, d_plan, d_in, d_err_in, d_err_out, maxprec, d_minexp, minexp_stride,
+                                           (uint32_t*)d_out, (uint64_t*)d_workspace, d_total_bits, d_index, shift,
+                                           hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

@@ -297,6 +297,17 @@ hipError_t launch_decode_mean_seg1d(const SegHeader& H, const void* d_plan, uint
                                     uint32_t stride_words, uint64_t stream_stride_words, const uint64_t* in,
                                     uint64_t stream_words, uint32_t nstreams, const uint64_t* index,
                                     uint64_t index_words, uint32_t chunk, void* out, int out_dtype, void* stream);
+// The residual form of the segmented encoder and the per-tensor tables of y = x + e (seg_resid1d.hip; include/gcow.h
+// "Segmented fields with a residual"). e_in: fp32 parallel to the buffer, null = zeros; e_out: fp32, may be e_in.
+// Stream, *d_total, index and ws as launch_encode_seg1d's for the fp32 array y; e_out receives finite(y - decode).
+hipError_t launch_encode_seg_resid1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
+                                     float* e_out, uint32_t maxprec, const int32_t* d_minexp, uint32_t stride_words,
+                                     uint32_t* out32, uint64_t* ws, uint64_t* d_total, uint64_t* index,
+                                     uint32_t index_shift, void* stream);
+// tables[s] (288 words, the caller's numbering, an all-zero row for an empty tensor): launch_rate_table1d_resid's table
+// of tensor s with its slice of e_in. ws: rate_table_rel_workspace_bytes(nsegs), zeroed by a kernel in stream order.
+hipError_t launch_rate_table_seg1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
+                                   uint32_t maxprec, uint64_t* tables, uint64_t* ws, void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

@@ -151,8 +151,12 @@ class GcowHookState:
     compressed_allgather_hook takes it too (with `target_bits`; _allgather_per_tensor): each rank fits its own
     gradients, sends one segmented stream (a minexp per tensor, read on the device) and its S fit records, 16 bytes
     per tensor, and every rank decodes and averages the W streams under the W sets in one launch. The bucket's
-    gradients must tile its flat buffer in order; a codec without encode_per_tensor / decode_mean_per_tensor, and
-    `error_feedback`: ValueError. Unset (the default): nothing changes."""
+    gradients must tile its flat buffer in order; a codec without encode_per_tensor / decode_mean_per_tensor:
+    ValueError. There `error_feedback` combines with it: each rank takes the per-tensor tables of bucket + carried
+    error, fits them and codes that sum with the segmented residual encode, which leaves each tensor's y - decode(y)
+    under its own fit in error_buffer(index, ...) (the codec's encode_residual_per_tensor; a codec without it:
+    ValueError before any codec call or collective). `reset_error_feedback()` forgets those buffers like the others.
+    Unset (the default): nothing changes."""
     params: GcowParams = field(default_factory=lambda: _codec.rate(16, 1))
     process_group: object = None
     codec: object = None  # None: gcow_amd.dist.device_codec()
@@ -537,15 +541,19 @@ def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[
     all-gather of the words, the all-gather of the index, and the all-gather of each rank's S fit records, 16 bytes per
     tensor: that is the wire format of the per-tensor minexp (word 0 of a record). Then one decode-mean straight into
     the bucket, stream r's tensor s under record (r, s). No table is all-reduced and no minexp reaches the host;
-    state.fit_record(index) is this rank's int64[S, 2] records."""
-    if state.error_feedback:
-        raise ValueError("per_tensor_budget on the wire has no residual form: error_feedback cannot be combined with it")
+    state.fit_record(index) is this rank's int64[S, 2] records. With state.error_feedback the tables are those of
+    bucket + carried error, the encode is the segmented residual form (the codec's encode_residual_per_tensor) and
+    state.error_buffer(index, ...) is updated in place; the wire format and the receive side are the same."""
     state.check_target()
     cdc = state.get_codec()
     missing = [m for m in ("encode_per_tensor", "decode_mean_per_tensor") if not hasattr(cdc, m)]
     if missing:
         raise ValueError("per_tensor_budget with compressed_allgather_hook needs a codec with %s "
                          "(gcow_amd.dist.DeviceCodec): %s" % (", ".join(missing), _PER_TENSOR_WIRE))
+    if state.error_feedback and not hasattr(cdc, "encode_residual_per_tensor"):
+        raise ValueError("error_feedback with per_tensor_budget needs a codec with encode_residual_per_tensor "
+                         "(gcow_amd.dist.DeviceCodec): the segmented encode of bucket + carried error that writes "
+                         "each tensor's residual under its own fit")
     if not (dist.is_available() and dist.is_initialized()):
         raise ValueError("compressed_allgather_hook with per_tensor_budget needs an initialised process group")
     group = state.process_group
@@ -560,8 +568,13 @@ def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[
     slot = bucket.index() if hasattr(bucket, "index") else None
     maxprec = state.params.maxprec
     cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
-    words, bits, index, fits = cdc.encode_per_tensor(flat, counts, state.target_bits, maxprec, INDEX_STRIDE,
-                                                     slot=("per_tensor", slot))
+    if state.error_feedback:  # the buffer is obtained here (zeros at first use, on this stream); it lives on the state
+        words, bits, index, fits = cdc.encode_residual_per_tensor(flat, state.error_buffer(slot, flat), counts,
+                                                                  state.target_bits, maxprec, INDEX_STRIDE,
+                                                                  slot=("per_tensor", slot))
+    else:
+        words, bits, index, fits = cdc.encode_per_tensor(flat, counts, state.target_bits, maxprec, INDEX_STRIDE,
+                                                         slot=("per_tensor", slot))
     state._fit_records[slot] = fits
     dev = flat.device
     if dev.type == "cuda":

@@ -240,6 +240,20 @@ class DeviceCodec:
         e, fits = enc(x, counts, index_stride)
         return e.words, e.bits_dev, e.index, fits
 
+    def encode_residual_per_tensor(self, x: torch.Tensor, err: torch.Tensor, counts, bits_per_value: float,
+                                   maxprec: int = 64, index_stride: int = 0, slot=None):
+        """`encode_per_tensor` with error feedback (codec.PerTensorFittedResidualEncoder: the per-tensor tables of
+        y = x + err, batch fit, segmented residual encode; no host read): -> (words, bits, index, fits), `err`
+        (fp32, parallel to x) updated in place with each tensor's y - decode(y) under its own fit. Cached per slot like
+        `encode_per_tensor`, in buffers apart from that method's."""
+        from . import codec
+        counts = tuple(int(c) for c in counts)
+        key = (slot, counts, x.dtype, x.device, float(bits_per_value), int(maxprec), index_stride, "per_tensor",
+               "residual")
+        enc = self._cached(key, lambda: codec.PerTensorFittedResidualEncoder(bits_per_value, maxprec))
+        e, fits = enc(x, err, counts, index_stride)
+        return e.words, e.bits_dev, e.index, fits
+
     def decode_mean_per_tensor(self, streams, stream_words: int, nstreams: int, counts, fits, maxprec: int = 64,
                                index=None, index_words: int = 0, index_stride: int = 16, out=None, slot=None):
         """The mean of nstreams segmented streams of one shape, each tensor under its stream's own fit

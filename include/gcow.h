@@ -720,6 +720,50 @@ gcow_status gcow_decode_mean_seg_device(const void* h_plan, const void* d_plan, 
                                         uint32_t index_stride, void* d_out, data_type out_dtype, void* hip_stream);
 
 /*
+ * Segmented fields with a residual: error feedback under a minexp per tensor. Both calls take a segmented field as
+ * defined above (plan, buffer, counts, words) and an error array parallel to the buffer:
+ *   - d_err_in: DEVICE fp32, n values, or NULL for zeros; 4-byte aligned, no more;
+ *   - d_err_out: DEVICE fp32, n values, 4-byte aligned; d_err_in == d_err_out is allowed (in place).
+ * e_s is the slice [off_s, off_s + n_s) of the error array, and y = (float)x + e one __fadd_rn per value (a bf16 x
+ * widened exactly), formed in registers and never stored. The plan is gcow_seg_plan's as it is: it holds no pointers, so
+ * one plan serves the tables, the encode and the decode.
+ *
+ * gcow_rate_table_seg_workspace_bytes: the workspace of the table call: 0 for a NULL, short or foreign plan, else
+ *   positive and a function of S only.
+ * gcow_rate_table_seg_device: d_tables is DEVICE uint64[S][288], rows in the caller's numbering. Row s is exactly what
+ *   gcow_rate_table_residual_device writes for tensor s as a field of its own with e_s: the table of y_s, its partial
+ *   last block padded from y as the encoder pads it, Inf / NaN blocks of y (an overflowing x + e included) under the
+ *   generic rule. An empty tensor gives an all-zero row. With d_err_in == NULL row s equals row s of
+ *   gcow_rate_table_rel_device for the same tensors. The tables are written whole and nothing past them; neither they
+ *   nor the workspace (8-byte aligned) need zeroing by the caller, and the workspace is zeroed by a kernel in stream
+ *   order. Integer sums only: the same bits run to run. No host read, no allocation; legal inside a stream capture.
+ * gcow_encode_seg_residual_device: stream, *d_total_bits and index are byte for byte what gcow_encode_seg_device writes
+ *   for the fp32 array y under the same words and a plan of the same counts. d_err_out over tensor s is what
+ *   gcow_encode_residual_device(t_s, {1, 16658, maxprec, clamp(word_s, -154, 133)}, e_s, ...) writes: e' = y - decode(y)
+ *   by one __fsub_rn, a non-finite result replaced by +0.0f. Only real values are written: a tensor's partial last
+ *   block does not reach the next tensor's first values, and nothing is written outside [d_err_out, d_err_out + n).
+ *   d_in is never written. Rows may start at any element-aligned address: whether a row moves as one vector is decided
+ *   at run time, per array, from its own address, so d_in, d_err_in and d_err_out may have three different alignments.
+ *   Capacity, workspace and index entries are the plan's queries (gcow_encode_seg_max_output_bytes, _workspace_bytes,
+ *   _index_entries); they depend on the counts only, not on the plan's dtype and not on the words. An empty list
+ *   writes *d_total_bits = 0 and nothing else. The launch count does not depend on S. No host read, no allocation;
+ *   legal inside a stream capture.
+ * Refusals, on the host before any launch: those of gcow_encode_seg_device, and GCOW_ERR_INVALID for a NULL d_err_out
+ * (non-empty list), an error pointer off 4 bytes, a NULL or misaligned (8 bytes) d_tables (S > 0), a workspace below its
+ * query.
+ */
+size_t gcow_rate_table_seg_workspace_bytes(const void* h_plan, size_t plan_bytes);
+gcow_status gcow_rate_table_seg_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                       const float* d_err_in, uint32_t maxprec, uint64_t* d_tables, void* d_workspace,
+                                       size_t workspace_bytes, void* hip_stream);
+gcow_status gcow_encode_seg_residual_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                            const float* d_err_in, float* d_err_out, uint32_t maxprec,
+                                            const int32_t* d_minexp, uint32_t minexp_stride, void* d_out,
+                                            size_t out_capacity, uint64_t* d_total_bits, void* d_workspace,
+                                            size_t workspace_bytes, uint64_t* d_index, uint32_t index_stride,
+                                            void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by
