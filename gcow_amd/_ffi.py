@@ -164,6 +164,7 @@ def load():
         "gcow_rate_table_seg_device": (i32, [vp, vp, sz, vp, vp, u32, vp, vp, sz, vp]),
         "gcow_encode_seg_residual_device": (i32, [vp, vp, sz, vp, vp, vp, u32, vp, u32, vp, sz, vp, vp, sz, vp, u32,
                                                   vp]),
+        "gcow_seg_rel_minexp_device": (i32, [vp, vp, sz, vp, vp, u32, vp, vp, u32, vp]),
         "gcow_decode_mean_seg_device": (i32, [vp, vp, sz, u32, vp, u32, u64, vp, sz, u64, u32, vp, u64, u32, vp, i32,
                                               vp]),
         "gcow_decode_device": (i32, [pi, pp, vp, sz, vp, u32, vp]),

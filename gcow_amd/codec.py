@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
+import numbers
 from dataclasses import dataclass
 
 import torch
@@ -1541,6 +1542,111 @@ class PerTensorFittedResidualEncoder:
         if counts:
             fit_device_batch(tables, self.budgets, self.minexp_floor, self.fits, stream)
         return self.enc(x, err, self.fits, None, stream), self.fits
+
+
+# ------------------------------------------------- segmented fields under a relative tolerance: words from one pass
+REL_BITS_MAX = 24
+
+
+def valid_rel_bits(rel_bits) -> bool:
+    """Whether rel_bits is an integer (Python's or numpy's; neither bool nor an integral float) in 0..24: the one test
+    of the codec entry points and of compressed_allgather_hook."""
+    return (isinstance(rel_bits, numbers.Integral) and not isinstance(rel_bits, bool)
+            and 0 <= rel_bits <= REL_BITS_MAX)
+
+
+def _check_rel_bits(rel_bits, what: str) -> int:
+    if not valid_rel_bits(rel_bits):
+        raise GcowError("%s: rel_bits must be an integer in 0..%d, got %r" % (what, REL_BITS_MAX, rel_bits))
+    return int(rel_bits)
+
+
+def relative_minexp_segmented(x: torch.Tensor, counts, rel_bits: int, err: torch.Tensor | None = None,
+                              absmax: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                              plan: SegmentPlan | None = None, stream=None) -> torch.Tensor:
+    """The per-tensor minexp words of a relative tolerance over a segmented field, from one pass on the device
+    (gcow_seg_rel_minexp_device): word s = max(emax_s - rel_bits, -94) (capped for a maximum in the top binade:
+    include/gcow.h), emax_s the exponent of the largest finite |x + err| of tensor s -- the word
+    roundtrip_tensors_relative codes tensor s under, and -94 for an empty tensor. x: the bucket, a contiguous 1-D fp32 /
+    bf16 device tensor of sum(counts) values; err: fp32, parallel to x, or None for zeros (y = x + err is formed in
+    registers, as encode_segmented_residual forms it). absmax: optional float32[S] device tensor that receives the
+    maxima (it is the call's workspace; default: new). out: int32[S] (packed words, stride 1; default: new) or an
+    int64[S, 2] array of gcow_fit records, of which only word 0 of each record is written. plan: a SegmentPlan of
+    these counts and x's dtype kept by the caller; without one every call makes and uploads a new SegmentPlan (a host
+    allocation and a copy), so only a call given plan, absmax and out allocates nothing and can be captured, as the
+    encoders below call it. No host read; at most three launches. -> out."""
+    what = "relative_minexp_segmented"
+    rel_bits = _check_rel_bits(rel_bits, what)
+    counts = tuple(int(c) for c in counts)
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise GcowError("%s expects a contiguous 1-D tensor on a device" % what)
+    pl = _seg_plan(plan, counts, x.dtype, x.device, what)
+    _check_seg_x(x, pl, x.device, what)
+    if err is not None:
+        _check_seg_err(x, err, what)
+    ns = len(counts)
+    if absmax is None:
+        absmax = torch.empty(ns, dtype=torch.float32, device=x.device)
+    elif not (isinstance(absmax, torch.Tensor) and absmax.is_cuda and absmax.device == x.device
+              and absmax.dtype == torch.float32 and absmax.is_contiguous() and absmax.numel() == ns):
+        raise GcowError("%s: absmax must be a contiguous float32 tensor of len(counts) values on x's device" % what)
+    if out is None:
+        out = torch.empty(ns, dtype=torch.int32, device=x.device)
+    ptr, stride = _fit_records(out, ns, x.device, what)
+    check(pl.L.gcow_seg_rel_minexp_device(pl.h.data_ptr(), pl.d.data_ptr(), pl.used, x.data_ptr() if pl.n else None,
+                                          err.data_ptr() if err is not None and pl.n else None, rel_bits,
+                                          absmax.data_ptr() if ns else None, ptr if ns else None, stride,
+                                          _stream_ptr(stream)), "gcow_seg_rel_minexp_device")
+    return out
+
+
+class PerTensorRelativeEncoder:
+    """A relative tolerance per tensor on the wire, with no host read: calling it with a bucket x (contiguous 1-D
+    device tensor) and the counts of its tensors launches the words pass (relative_minexp_segmented) and the segmented
+    encode under those words. -> (Encoded, words): words is the int32[S] tensor of per-tensor minexp, what a receiver
+    needs to decode (4 bytes per tensor); `absmax` holds the last call's maxima. Buffers and plan are made at the first
+    call for a shape; later calls allocate nothing and do nothing on the host between the launches, so the chain
+    captures into one graph that follows the data it is replayed on."""
+
+    residual = False
+
+    def __init__(self, rel_bits: int, maxprec: int = 64):
+        self.rel_bits, self.maxprec = _check_rel_bits(rel_bits, type(self).__name__), int(maxprec)
+        self.enc = self.words = self.absmax = None
+        self._key = None
+
+    def _prepare(self, x, counts, index_stride):
+        counts = tuple(int(c) for c in counts)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 1 and x.is_contiguous()
+                and x.numel() == sum(counts)):
+            raise GcowError("%s expects a contiguous 1-D device tensor of sum(counts) values" % type(self).__name__)
+        key = (counts, x.dtype, x.device, int(index_stride))
+        if key != self._key:
+            make = SegmentedResidualEncoder if self.residual else SegmentedEncoder
+            self.enc = make(counts, x.dtype, self.maxprec, x.device, index_stride)
+            self.words = torch.zeros(len(counts), dtype=torch.int32, device=x.device)
+            self.absmax = torch.zeros(len(counts), dtype=torch.float32, device=x.device)
+            self._key = key
+        return counts
+
+    def __call__(self, x: torch.Tensor, counts, index_stride: int = 0, stream=None):
+        counts = self._prepare(x, counts, index_stride)
+        relative_minexp_segmented(x, counts, self.rel_bits, None, self.absmax, self.words, self.enc.plan, stream)
+        return self.enc(x, self.words, stream), self.words
+
+
+class PerTensorRelativeResidualEncoder(PerTensorRelativeEncoder):
+    """PerTensorRelativeEncoder with error feedback: calling it with a bucket x, the carried error err (fp32, parallel
+    to x, updated in place), the counts and an index stride launches the words pass over y = x + err -- the maxima are
+    of the values that are coded -- and the segmented residual encode under those words, which leaves each tensor's
+    y - decode(y) in err. -> (Encoded, words) as PerTensorRelativeEncoder. One SegmentPlan serves both calls."""
+
+    residual = True
+
+    def __call__(self, x: torch.Tensor, err: torch.Tensor, counts, index_stride: int = 0, stream=None):
+        counts = self._prepare(x, counts, index_stride)
+        relative_minexp_segmented(x, counts, self.rel_bits, err, self.absmax, self.words, self.enc.plan, stream)
+        return self.enc(x, err, self.words, None, stream), self.words
 
 
 def stitch(dst: torch.Tensor, dst_bit_offset: int, src: torch.Tensor, src_bits: int, stream=None):

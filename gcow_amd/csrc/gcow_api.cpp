@@ -1962,6 +1962,30 @@ gcow_status gcow_encode_seg_residual_device(const void* h_plan, const void* d_pl
   return GCOW_OK;
 }
 
+// ----------------------------------------------------------------- relative tolerance over a segmented field
+gcow_status gcow_seg_rel_minexp_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                       const float* d_err_in, uint32_t rel_bits, float* d_absmax, int32_t* d_minexp,
+                                       uint32_t minexp_stride, void* hip_stream)
+{
+  gcow::SegHeader H;
+  gcow_status st = seg_header(h_plan, plan_bytes, H);
+  if (st) return st;
+  if (rel_bits > gcow::kRtRelMaxBits) return fail(GCOW_ERR_INVALID, "rel_bits above 24");
+  if (!H.nsegs) return GCOW_OK;  // no tensor: no word
+  if (!d_absmax || (uintptr_t)d_absmax % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_absmax");
+  if (!d_minexp || (uintptr_t)d_minexp % 4) return fail(GCOW_ERR_INVALID, "null or misaligned d_minexp");
+  if (!minexp_stride) return fail(GCOW_ERR_INVALID, "a stride of 0 words");
+  if (H.nvb) {
+    if (!d_plan || (uintptr_t)d_plan % 8) return fail(GCOW_ERR_INVALID, "null or misaligned device plan");
+    if (!d_in || (uintptr_t)d_in % (H.dtype == gcow::DT_BF16 ? 2 : 4))
+      return fail(GCOW_ERR_INVALID, "null input, or misaligned for its element type");
+    if ((uintptr_t)d_err_in % 4) return fail(GCOW_ERR_INVALID, "misaligned d_err_in");
+  }
+  GCOW_HIP(gcow::launch_seg_rel_minexp1d(H, d_plan, d_in, d_err_in, rel_bits, (uint32_t*)d_absmax, d_minexp,
+                                         minexp_stride, hip_stream));
+  return GCOW_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- zfp header
 // Restates libzfp 0.5.5 zfp_field_metadata / zfp_stream_mode / zfp_write_header / zfp_read_header / zfp_stream_set_mode
 // (third-party format; pinned by tests/golden/libzfp_headers.json).

@@ -308,6 +308,13 @@ hipError_t launch_encode_seg_resid1d(const SegHeader& H, const void* d_plan, con
 // of tensor s with its slice of e_in. ws: rate_table_rel_workspace_bytes(nsegs), zeroed by a kernel in stream order.
 hipError_t launch_rate_table_seg1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
                                    uint32_t maxprec, uint64_t* tables, uint64_t* ws, void* stream);
+// The words of a relative tolerance over a segmented field (seg_resid1d.hip; include/gcow.h "Relative tolerance over a
+// segmented field"): absmax[s] (nsegs words, zeroed by a kernel in stream order) = the largest finite |fadd(x, e_in)| of
+// tensor s as bits, and d_minexp[s * stride_words] = rel_minexp(absmax[s], rel_bits) (rel_minexp.h), an empty tensor's
+// the floor. At most three launches: zero, the pass over min(ntiles, kRateTableRelMaxGrid) runs of tiles, the words.
+hipError_t launch_seg_rel_minexp1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
+                                   uint32_t rel_bits, uint32_t* absmax, int32_t* d_minexp, uint32_t stride_words,
+                                   void* stream);
 hipError_t launch_copy_pattern1d(const void* in, int dtype, uint64_t nvals, uint32_t wb, void* out, void* stream);
 // *flag = 0, then 1 if a[i] != b[i] for any i < n
 hipError_t launch_words_differ(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* flag, void* stream);

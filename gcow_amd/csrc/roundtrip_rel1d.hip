@@ -30,6 +30,7 @@
 
 #include "field_io.h"
 #include "rel_locate.h"
+#include "rel_minexp.h"
 #include "roundtrip1d.h"
 #include "var1d_prep.h"
 
@@ -41,29 +42,11 @@ static_assert(kRtRelGatherBlocks <= kRtListChunkBlocks, "a gather chunk fits the
 typedef unsigned int rel_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned int rel_v4u __attribute__((ext_vector_type(4)));
 
-// |x| as bits, 0 for Inf / NaN
-__device__ __forceinline__ uint32_t rel_mag(uint32_t bits)
-{
-  const uint32_t a = bits & 0x7fffffffu;
-  return a < 0x7f800000u ? a : 0u;
-}
-
-// The tensor's parameter set from its largest finite magnitude (as bits): emax = (a >> 23) - 126, a subnormal or zero
-// maximum gives -126. The floor keeps every block whose values all cast to INT_MIN (emax <= -98) at precision 0.
-// The headroom cap keeps the decode finite: a value decodes to within 2^minexp of itself, so a tensor whose maximum
-// lies in the top binade (emax = 128) needs a + 2^minexp < 2^128, or a finite value near the maximum comes back as
-// Inf. With g = 2^128 - a = (2^24 - mantissa) 2^104 and hexp = floor(log2 g), minexp <= hexp - 2 leaves
-// |decode| <= 2^128 - 3 g / 4, which is below the fp32 rounding boundary 2^128 - 2^103 since g >= 2^104. For
-// emax <= 127, a + 2^minexp < 2^128 holds by itself and the cap is absent.
+// The tensor's parameter set from its largest finite magnitude (as bits): minexp by rel_minexp (rel_minexp.h, the one
+// definition of the rule: the floor at -94 and the headroom cap of a maximum in the top binade are explained there).
 __device__ __forceinline__ Params rel_params(uint32_t a, uint32_t rel_bits, uint32_t maxprec)
 {
-  const uint32_t E = a >> 23;
-  int minexp = max((int)E - 126 - (int)rel_bits, kRtRelMinExpFloor);
-  if (E == 254u) {
-    const uint32_t gap = 0x1000000u - ((a & 0x7fffffu) | 0x800000u);  // 1 .. 2^23, in units of 2^104
-    minexp = min(minexp, 104 + (31 - (int)__builtin_clz(gap)) - kRtRelHeadroom);
-  }
-  return Params{1u, 16658u, maxprec, minexp};
+  return Params{1u, 16658u, maxprec, rel_minexp(a, rel_bits)};
 }
 
 // Where a tensor's parameter set comes from. Both kernels below are templates over it, called once per workgroup

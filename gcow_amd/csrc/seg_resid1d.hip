@@ -32,6 +32,15 @@
 // number of that tensor's blocks inside the tile to its count word, as rate_table_rel1d.hip counts gather pieces. The
 // workspace is rate_table_rel1d.hip's (kRateTableRelWords per tensor, the caller's numbering), zeroed by a kernel in
 // stream order; launch_rate_table_finish_batch turns it into the rows. Integer adds only.
+//
+// The maximum pass, k_seg_absmax (gcow_seg_rel_minexp_device): the table pass's runs and loads, with
+// the largest finite |y| per tensor as the only result. |y| is taken as integer bits with Inf / NaN masked to 0
+// (rel_mag), so an unsigned maximum is the maximum magnitude and a padding value, a copy of a real one, cannot change
+// it. A uniform tile updates one register per lane, reduced over the workgroup into one atomicMax when the run moves
+// to another tensor and at its end; the blocks of a mixed tile go to their tensors' slots, one atomic per wave where
+// the lanes that have something share a tensor (k_rel_absmax's shortcut), else one per lane. A zero maximum issues no
+// atomic: the slots are zeroed by k_seg_absmax_zero in stream order. k_seg_rel_words turns slot s into the word
+// rel_minexp(a_s, rel_bits) (rel_minexp.h) at d_minexp[s * stride]. Integer maxima only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -41,6 +50,7 @@
 #include "field_io.h"
 #include "kernels.h"
 #include "rate_table1d.h"
+#include "rel_minexp.h"
 #include "seg1d.h"
 #include "tiles.h"
 #include "var1d_prep.h"
@@ -455,7 +465,115 @@ __global__ __launch_bounds__(RTT) void k_rate_table_seg(SegPlanDev P, const void
   }
 }
 
+// ---------------------------------------------------------------------------------------- the maximum and the words
+__global__ __launch_bounds__(256) void k_seg_absmax_zero(uint32_t* __restrict__ absmax, uint32_t nsegs)
+{
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nsegs; i += gridDim.x * 256u) absmax[i] = 0u;
+}
+
+// the largest of a block's four magnitudes (a missing block holds zeros)
+__device__ __forceinline__ uint32_t seg_block_mag(const float* f)
+{
+  return max(max(rel_mag(__float_as_uint(f[0])), rel_mag(__float_as_uint(f[1]))),
+             max(rel_mag(__float_as_uint(f[2])), rel_mag(__float_as_uint(f[3]))));
+}
+
+__device__ __forceinline__ uint32_t seg_wave_max(uint32_t m)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+  return m;
+}
+
+// The workgroup's maximum into the tensor's slot: one atomic, none for zero. Every lane of the workgroup calls it.
+__device__ __forceinline__ void seg_absmax_flush(uint32_t m, uint32_t seg, uint32_t* sh, uint32_t* absmax)
+{
+  m = seg_wave_max(m);
+  if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t mm = sh[0];
+#pragma unroll
+    for (uint32_t w = 1; w < RTT / 64; w++) mm = max(mm, sh[w]);
+    if (mm) atomicMax(absmax + seg, mm);
+  }
+  __syncthreads();  // sh is written again by the next flush
+}
+
+template <int DT>
+__global__ __launch_bounds__(RTT) void k_seg_absmax(SegPlanDev P, const void* __restrict__ in,
+                                                    const float* __restrict__ e_in, uint32_t nruns, uint32_t* absmax)
+{
+  __shared__ uint32_t sh[RTT / 64];
+  // run r of nruns <= ntiles: tiles t0 .. t1 - 1, at least one (k_rate_table_seg's cut)
+  const uint32_t r = blockIdx.x;
+  const uint32_t t0 = (uint32_t)((uint64_t)r * P.ntiles / nruns), t1 = (uint32_t)((uint64_t)(r + 1) * P.ntiles / nruns);
+  uint32_t seg = ~0u;  // the tensor whose maximum m holds (none yet)
+  uint32_t m = 0;
+  for (uint32_t t = t0; t < t1; t++) {
+    const uint32_t tw = P.tiles[t];  // uniform over the workgroup
+    SegYLane<DT, true> L;
+    L.load(P, in, e_in, nullptr, 0u, t);
+    if (tw >> 31) {  // whole blocks of one tensor
+      const uint32_t s = P.ents[tw & 0x7fffffffu].seg;
+      if (s != seg) {
+        if (seg != ~0u) seg_absmax_flush(m, seg, sh, absmax);  // the run moves on to another tensor
+        seg = s;
+        m = 0;
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < RTU; k++) m = max(m, seg_block_mag(L.y.f[k]));
+    } else {  // blocks of several tensors, or a partial last block: each to its tensor's slot
+#pragma unroll
+      for (uint32_t k = 0; k < RTU; k++) {
+        const uint32_t mk = seg_block_mag(L.y.f[k]), sk = L.seg[k];
+        // lanes with mk = 0 have nothing to add; where the others of the wave share a tensor, one atomic serves them
+        const uint64_t need = __ballot(mk != 0u);
+        if (need == 0ull) continue;
+        const uint32_t sref = (uint32_t)__shfl((int)sk, __ffsll((unsigned long long)need) - 1, 64);
+        if (__all(mk == 0u || sk == sref)) {
+          const uint32_t w = seg_wave_max(mk);
+          if ((threadIdx.x & 63u) == 0) atomicMax(absmax + sref, w);
+        } else if (mk != 0u) {
+          atomicMax(absmax + sk, mk);
+        }
+      }
+    }
+  }
+  if (seg != ~0u) seg_absmax_flush(m, seg, sh, absmax);  // uniform
+}
+
+// slot s -> the word of tensor s; an empty tensor's slot is 0, whose word is the floor
+__global__ __launch_bounds__(256) void k_seg_rel_words(const uint32_t* __restrict__ absmax, uint32_t nsegs,
+                                                       uint32_t rel_bits, int32_t* __restrict__ minexp, uint32_t stride)
+{
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nsegs; i += gridDim.x * 256u)
+    minexp[(uint64_t)i * stride] = rel_minexp(absmax[i], rel_bits);
+}
+
 }  // namespace
+
+// zero -> pass -> words
+hipError_t launch_seg_rel_minexp1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
+                                   uint32_t rel_bits, uint32_t* absmax, int32_t* d_minexp, uint32_t stride_words,
+                                   void* stream)
+{
+  hipStream_t st = (hipStream_t)stream;
+  if (!H.nsegs) return hipSuccess;
+  const uint32_t ng = std::min((H.nsegs + 255u) / 256u, 64u);
+  k_seg_absmax_zero<<<ng, 256, 0, st>>>(absmax, H.nsegs);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (H.ntiles) {
+    const SegPlanDev P = seg_plan_dev(H, d_plan);
+    const uint32_t nruns = std::min(H.ntiles, kRateTableRelMaxGrid);
+    if (H.dtype == DT_BF16) k_seg_absmax<DT_BF16><<<nruns, RTT, 0, st>>>(P, in, e_in, nruns, absmax);
+    else k_seg_absmax<DT_F32><<<nruns, RTT, 0, st>>>(P, in, e_in, nruns, absmax);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  k_seg_rel_words<<<ng, 256, 0, st>>>(absmax, H.nsegs, rel_bits, d_minexp, stride_words);
+  return hipGetLastError();
+}
 
 hipError_t launch_encode_seg_resid1d(const SegHeader& H, const void* d_plan, const void* in, const float* e_in,
                                      float* e_out, uint32_t maxprec, const int32_t* d_minexp, uint32_t stride_words,

@@ -85,12 +85,24 @@ class GcowHookState:
     7/8 (2n + 4n) at W = 8. The mean is coded from its fp32 values whatever the bucket's dtype: for a bf16 bucket the
     second stage saves bytes only below 16 bits per value. Unset (the default): nothing changes.
 
-    `relative_bits` (roundtrip_hook only; the two wire hooks raise ValueError with it set: their decoder would need the
-    per-tensor exponents on the wire): after the mean all-reduce every parameter's gradient in the bucket
-    (bucket.gradients(), views of the buffer) is round-tripped in place as a field of its own, in accuracy mode under
-    a tolerance of 2^-relative_bits relative to that gradient's largest magnitude (codec.roundtrip_tensors_relative,
-    through the codec's roundtrip_relative, cached per bucket). `params` contributes only its maxprec. The bucket must
-    be fp32 or bf16. Unset (the default): nothing changes.
+    `relative_bits` (roundtrip_hook and compressed_allgather_hook; compressed_sharded_hook raises ValueError with it
+    set: its pieces carry no per-tensor exponents): roundtrip_hook -- after the mean all-reduce every parameter's
+    gradient in the bucket (bucket.gradients(), views of the buffer) is round-tripped in place as a field of its own,
+    in accuracy mode under a tolerance of 2^-relative_bits relative to that gradient's largest magnitude
+    (codec.roundtrip_tensors_relative, through the codec's roundtrip_relative, cached per bucket).
+    compressed_allgather_hook (_allgather_relative) -- each rank takes its own gradients' maxima in one pass on the
+    device, sends one segmented stream coded under the resulting minexp word per gradient and its S int32 words,
+    4 bytes per tensor, and every rank decodes and averages the W streams under the W word sets in one launch
+    (the codec's encode_relative / decode_mean_per_tensor). Nothing is read on the host but the gathered lengths. The
+    bucket's gradients must tile its flat buffer in order. With `error_feedback` the maxima are those of bucket +
+    carried error, the values that are coded, and the segmented residual encode leaves each tensor's y - decode(y)
+    under its own word in error_buffer(index, ...) (the codec's encode_residual_relative). ValueError, before any
+    codec call or collective: with `compress_mean`, `target_bits` or `per_tensor_budget` (both choose the tolerance);
+    a value outside 0..24 (bool and float are no integers here: codec.valid_rel_bits); a codec without those methods;
+    no initialised process group. In both hooks `params` contributes only its maxprec -- a fixed-rate set, the default
+    included, serves as well as a variable-rate one: the exchange is the variable-rate one either way, so setup()
+    creates the exchange group whenever the field is set -- and the bucket must be fp32 or bf16. Unset (the default):
+    nothing changes.
 
     `target_bits` (all three hooks): accuracy mode under a bit budget of target_bits bits per value. `params` must be
     a variable-rate set without a block budget (accuracy, precision, expert with minbits <= 1 and maxbits >= 160),
@@ -169,7 +181,8 @@ class GcowHookState:
     # compressed_sharded_hook: the mean shards travel compressed too (class docstring); the other hooks refuse it
     compress_mean: bool = False
     mean_params: GcowParams | None = None  # the mean's parameter set; None: `params`
-    # roundtrip_hook: a tolerance relative to each parameter's gradient (class docstring); the wire hooks refuse it
+    # roundtrip_hook, compressed_allgather_hook: a tolerance relative to each parameter's gradient (class docstring);
+    # compressed_sharded_hook refuses it
     relative_bits: int | None = None
     # accuracy mode under a budget of this many bits per value (class docstring)
     target_bits: float | None = None
@@ -194,10 +207,13 @@ class GcowHookState:
 
     def needs_comm_group(self) -> bool:
         """A multi-rank state whose hook runs collectives on the comm thread: variable rate (the all-gather hook's
-        length exchange) or the sharded hook at any rate. The fixed-rate all-gather and round-trip hooks issue theirs
-        from the autograd thread on `process_group` and get no extra communicator."""
+        length exchange), the sharded hook at any rate, or `relative_bits` whatever `params` is (the all-gather hook
+        then runs the segmented, variable-rate exchange and takes only maxprec from `params`). The fixed-rate
+        all-gather and round-trip hooks issue theirs from the autograd thread on `process_group` and get no extra
+        communicator. The state does not know its hook: one registered with roundtrip_hook under variable-rate
+        `params` or `relative_bits` gets a group it does not use."""
         return (dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1
-                and (self.sharded or not _codec.is_fixed(self.params)))
+                and (self.sharded or self.relative_bits is not None or not _codec.is_fixed(self.params)))
 
     def setup(self) -> "GcowHookState":
         """Create the exchange's process group (a collective over `process_group`'s ranks; a no-op for a one-rank
@@ -389,8 +405,9 @@ def _fit_next(state: GcowHookState, table: torch.Tensor, index, n: int, world: i
 _PER_TENSOR_WIRE = ("per_tensor_budget is for roundtrip_hook and compressed_allgather_hook: a stream coded under a "
                     "minexp per tensor needs them on the wire to be decoded, which only the all-gather hook's segmented "
                     "exchange sends")
-_RELATIVE_WIRE = ("relative_bits is for roundtrip_hook: a stream coded under per-tensor exponents needs them on the "
-                  "wire to be decoded, which the wire hooks do not send")
+_RELATIVE_WIRE = ("relative_bits is for roundtrip_hook and compressed_allgather_hook: a stream coded under per-tensor "
+                  "exponents needs them on the wire to be decoded, which only the all-gather hook's segmented exchange "
+                  "sends; compressed_sharded_hook's pieces carry none")
 
 
 def roundtrip_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
@@ -514,22 +531,22 @@ class _CommWorker:
         return fut
 
 
-def _bucket_counts(bucket, buf: torch.Tensor):
+def _bucket_counts(bucket, buf: torch.Tensor, what: str = "per_tensor_budget"):
     """The sizes of the bucket's gradients when they tile its flat buffer in order (pointer arithmetic), else
-    ValueError: the segmented stream is cut where the gradients lie."""
+    ValueError: the segmented stream is cut where the gradients lie. what: the mode that asks, for the message."""
     grads = list(bucket.gradients())
     at, esz = buf.data_ptr(), buf.element_size()
     counts = []
     for g in grads:
         n = g.numel()
         if g.dtype != buf.dtype or (n and (not g.is_contiguous() or g.data_ptr() != at)):
-            raise ValueError("per_tensor_budget on the wire: the bucket's gradients must tile its flat buffer in "
-                             "order (gradient %d does not lie where the one before it ends)" % len(counts))
+            raise ValueError("%s on the wire: the bucket's gradients must tile its flat buffer in "
+                             "order (gradient %d does not lie where the one before it ends)" % (what, len(counts)))
         counts.append(n)
         at += n * esz
     if sum(counts) != buf.numel():
-        raise ValueError("per_tensor_budget on the wire: the bucket's gradients cover %d of its %d values"
-                         % (sum(counts), buf.numel()))
+        raise ValueError("%s on the wire: the bucket's gradients cover %d of its %d values"
+                         % (what, sum(counts), buf.numel()))
     return counts
 
 
@@ -576,6 +593,16 @@ def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[
         words, bits, index, fits = cdc.encode_per_tensor(flat, counts, state.target_bits, maxprec, INDEX_STRIDE,
                                                          slot=("per_tensor", slot))
     state._fit_records[slot] = fits
+    return _segmented_exchange(state, cdc, buf, flat, counts, words, bits, index, fits, maxprec, world, cgroup,
+                               ("per_tensor", slot))
+
+
+def _segmented_exchange(state: GcowHookState, cdc, buf, flat, counts, words, bits, index, sets, maxprec, world, cgroup,
+                        slot) -> torch.futures.Future[torch.Tensor]:
+    """The comm-thread half of the segmented hooks: a rank's segmented stream (words, bits, index at INDEX_STRIDE) and
+    its per-tensor sets -- int64[S, 2] fit records, 16 bytes per tensor (minexp | status << 32, bits), or int32[S]
+    minexp words, 4 bytes per tensor -- are all-gathered, and one decode-mean writes the bucket, stream r's tensor s
+    under set (r, s). The gathered lengths are the one host read."""
     dev = flat.device
     if dev.type == "cuda":
         ev = torch.cuda.Event()
@@ -593,7 +620,7 @@ def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[
         with ctx:
             if side is not None:
                 side.wait_event(ev)
-                for t in (words, bits, index, fits):
+                for t in (words, bits, index, sets):
                     t.record_stream(side)
             lens, lens_h = gdist.gather_lengths(bits, dev, cgroup)  # host read: this thread waits, autograd does not
             maxw = max(1, max((b + 63) // 64 for b in lens_h))
@@ -602,14 +629,69 @@ def _allgather_per_tensor(state: GcowHookState, bucket) -> torch.futures.Future[
             ni = index.numel()
             idx = torch.empty(world * ni, dtype=torch.int64, device=dev)
             gdist.allgather_into(idx, index[:ni].contiguous(), cgroup)
-            mine = fits.reshape(-1).contiguous()  # S records of 16 bytes: minexp | status << 32, bits
-            recs = torch.empty(world * mine.numel(), dtype=torch.int64, device=dev)
+            mine = sets.reshape(-1).contiguous()
+            recs = torch.empty(world * mine.numel(), dtype=mine.dtype, device=dev)
             gdist.allgather_into(recs, mine, cgroup)
             cdc.decode_mean_per_tensor(gathered, maxw, world, counts, recs, maxprec, idx, ni, INDEX_STRIDE, out=flat,
-                                       slot=("per_tensor", slot))
+                                       slot=slot)
             fut.set_result(buf)
 
     return state.worker().submit(exchange, fut)
+
+
+def _allgather_relative(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
+    """compressed_allgather_hook with relative_bits: every rank codes each gradient of the bucket under a tolerance of
+    2^-relative_bits of that gradient's own largest magnitude. On the autograd thread, with nothing read back: one pass
+    over the bucket leaves a minexp word per gradient (the codec's encode_relative: the words pass, then the segmented
+    encode under those words, with a 16-block index). On the comm thread (_segmented_exchange): the gathered lengths,
+    the padded all-gather of the streams, the all-gather of the index and the all-gather of each rank's S int32 words --
+    the wire format, 4 bytes per tensor -- then one decode-mean straight into the bucket, stream r's tensor s under
+    word (r, s). `params` contributes only its maxprec. With state.error_feedback the words are those of bucket +
+    carried error, the encode is the segmented residual form (encode_residual_relative) and
+    state.error_buffer(index, ...) is updated in place; the wire format and the receive side are the same.
+    Every refusal is a ValueError naming relative_bits, raised before any codec call or collective."""
+    rel = state.relative_bits
+    if state.compress_mean:
+        raise ValueError("relative_bits with compress_mean: compress_mean is for compressed_sharded_hook (its "
+                         "all-gather of the mean shards); compressed_allgather_hook sends no mean")
+    try:
+        state.check_target()  # target_bits and relative_bits both choose the tolerance
+    except ValueError as ex:
+        if "relative_bits" in str(ex):
+            raise
+        raise ValueError("relative_bits with a budget mode: %s" % ex) from None
+    if state.per_tensor_budget:
+        raise ValueError("per_tensor_budget (with target_bits) and relative_bits both choose the tolerance: set one")
+    if not _codec.valid_rel_bits(rel):
+        raise ValueError("relative_bits must be an integer in 0..%d, got %r" % (_codec.REL_BITS_MAX, rel))
+    cdc = state.get_codec()
+    need = ("encode_relative", "decode_mean_per_tensor") + (("encode_residual_relative",) if state.error_feedback else ())
+    missing = [m for m in need if not hasattr(cdc, m)]
+    if missing:
+        raise ValueError("relative_bits with compressed_allgather_hook%s needs a codec with %s "
+                         "(gcow_amd.dist.DeviceCodec)" % (" and error_feedback" if state.error_feedback else "",
+                                                          ", ".join(missing)))
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError("compressed_allgather_hook with relative_bits needs an initialised process group")
+    group = state.process_group
+    buf = bucket.buffer()
+    if buf.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("relative_bits takes fp32 or bf16 buckets, got %s" % buf.dtype)
+    flat = buf.reshape(-1)
+    if not flat.is_contiguous() or flat.data_ptr() != buf.data_ptr():
+        raise ValueError("relative_bits on the wire takes a contiguous bucket buffer")
+    counts = _bucket_counts(bucket, flat, "relative_bits")
+    world = dist.get_world_size(group)
+    slot = bucket.index() if hasattr(bucket, "index") else None
+    maxprec = state.params.maxprec
+    cgroup = state.comm_group() if world > 1 else group  # raises here, on the autograd thread, without setup()
+    if state.error_feedback:  # the buffer is obtained here (zeros at first use, on this stream); it lives on the state
+        words, bits, index, mx = cdc.encode_residual_relative(flat, state.error_buffer(slot, flat), counts, rel,
+                                                              maxprec, INDEX_STRIDE, slot=("relative", slot))
+    else:
+        words, bits, index, mx = cdc.encode_relative(flat, counts, rel, maxprec, INDEX_STRIDE, slot=("relative", slot))
+    return _segmented_exchange(state, cdc, buf, flat, counts, words, bits, index, mx, maxprec, world, cgroup,
+                               ("relative", slot))
 
 
 def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Future[torch.Tensor]:
@@ -621,11 +703,11 @@ def compressed_allgather_hook(state: GcowHookState, bucket) -> torch.futures.Fut
     padded all-gather; that read and the collectives after it run on the state's comm thread (on a side stream that
     waits for the encode), and the returned future completes when the mean is written. Each bucket encodes into its
     own buffers (slot = bucket index), so a later bucket's encode never overwrites a stream still in flight."""
+    if state.relative_bits is not None:  # ahead of the checks below: its refusals, compress_mean's too, name the field
+        return _allgather_relative(state, bucket)
     if state.compress_mean:
         raise ValueError("compress_mean is for compressed_sharded_hook (its all-gather of the mean shards): "
                          "compressed_allgather_hook decodes every rank's stream on every rank and sends no mean")
-    if state.relative_bits is not None:
-        raise ValueError(_RELATIVE_WIRE)
     if state.per_tensor_budget:
         return _allgather_per_tensor(state, bucket)
     state.check_target()

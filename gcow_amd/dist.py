@@ -254,6 +254,33 @@ class DeviceCodec:
         e, fits = enc(x, err, counts, index_stride)
         return e.words, e.bits_dev, e.index, fits
 
+    def encode_relative(self, x: torch.Tensor, counts, rel_bits: int, maxprec: int = 64, index_stride: int = 0,
+                        slot=None):
+        """The bucket x (contiguous 1-D, its tensors `counts` values each, in order) encoded under a tolerance of
+        2^-rel_bits of each tensor's own largest magnitude (codec.PerTensorRelativeEncoder: the words pass, then the
+        segmented encode; no host read): -> (words, bits, index, minexp_words), minexp_words the int32[S] words a
+        receiver decodes under (decode_mean_per_tensor takes them as `fits`). Cached per (slot, counts, dtype, device,
+        rel_bits, maxprec, index stride) like the encoders."""
+        from . import codec
+        counts = tuple(int(c) for c in counts)
+        key = (slot, counts, x.dtype, x.device, int(rel_bits), int(maxprec), index_stride, "relative_wire")
+        enc = self._cached(key, lambda: codec.PerTensorRelativeEncoder(rel_bits, maxprec))
+        e, words = enc(x, counts, index_stride)
+        return e.words, e.bits_dev, e.index, words
+
+    def encode_residual_relative(self, x: torch.Tensor, err: torch.Tensor, counts, rel_bits: int, maxprec: int = 64,
+                                 index_stride: int = 0, slot=None):
+        """`encode_relative` with error feedback (codec.PerTensorRelativeResidualEncoder: the words of y = x + err,
+        then the segmented residual encode under them; no host read): -> (words, bits, index, minexp_words), `err`
+        (fp32, parallel to x) updated in place with each tensor's y - decode(y) under its own word. Cached per slot
+        like `encode_relative`, in buffers apart from that method's."""
+        from . import codec
+        counts = tuple(int(c) for c in counts)
+        key = (slot, counts, x.dtype, x.device, int(rel_bits), int(maxprec), index_stride, "relative_wire", "residual")
+        enc = self._cached(key, lambda: codec.PerTensorRelativeResidualEncoder(rel_bits, maxprec))
+        e, words = enc(x, err, counts, index_stride)
+        return e.words, e.bits_dev, e.index, words
+
     def decode_mean_per_tensor(self, streams, stream_words: int, nstreams: int, counts, fits, maxprec: int = 64,
                                index=None, index_words: int = 0, index_stride: int = 16, out=None, slot=None):
         """The mean of nstreams segmented streams of one shape, each tensor under its stream's own fit

@@ -764,6 +764,34 @@ gcow_status gcow_encode_seg_residual_device(const void* h_plan, const void* d_pl
                                             void* hip_stream);
 
 /*
+ * Relative tolerance over a segmented field: the per-tensor minexp words of gcow_roundtrip_rel_device's rule from one
+ * pass over the buffer, written where the segmented calls above read them. The field is a segmented field as defined
+ * above (gcow_seg_plan's plan, unchanged; d_in fp32 or bf16 at any element-aligned address) and d_err_in the error array
+ * of the residual calls: DEVICE fp32 parallel to the buffer, 4-byte aligned, or NULL for zeros.
+ *
+ * gcow_seg_rel_minexp_device: for every tensor s of the caller's numbering,
+ *   - y = (float)x + e, one __fadd_rn per value, formed in registers as gcow_encode_seg_residual_device forms it and never
+ *     stored (a bf16 x widened exactly; without e this is x + 0);
+ *   - d_absmax[s] = a_s, the largest finite |y| over the tensor's real values, as a float: Inf / NaN are left out, an
+ *     overflowing x + e too; +0 when no value is finite, and for an empty tensor;
+ *   - d_minexp[s * minexp_stride] = max(emax_s - rel_bits, -94), emax_s the block-exponent of a_s (-126 for zero and
+ *     subnormals), and for emax_s = 128 additionally at most floor(log2(2^128 - a_s)) - 2: exactly the word tensor s is
+ *     coded under by gcow_roundtrip_rel_device (one definition serves both calls). An empty tensor gets the word of
+ *     a = 0, which is -94, so the words are deterministic.
+ *   Only those words are written: with minexp_stride 4 (an array of gcow_fit) the other three words of each record stay
+ *   as they were; with 1 the words are packed. d_absmax (S floats) doubles as the workspace and is zeroed by a kernel in
+ *   stream order; it is required when S > 0. At most three launches whatever S is (zero, pass, words); integer maxima
+ *   only: the same bits run to run. No host read, no allocation; legal inside a stream capture.
+ * Refusals, on the host before any launch: GCOW_ERR_INVALID for a NULL, short or foreign plan; for rel_bits > 24; with
+ * S > 0 for a NULL or misaligned (4 bytes) d_absmax or d_minexp or a minexp_stride of 0; with values present for a NULL
+ * or misaligned (8 bytes) d_plan, a NULL d_in or one misaligned for its element type, a d_err_in off 4 bytes. An empty
+ * list returns GCOW_OK and writes nothing.
+ */
+gcow_status gcow_seg_rel_minexp_device(const void* h_plan, const void* d_plan, size_t plan_bytes, const void* d_in,
+                                       const float* d_err_in, uint32_t rel_bits, float* d_absmax, int32_t* d_minexp,
+                                       uint32_t minexp_stride, void* hip_stream);
+
+/*
  * Decode d_in into field->data (DEVICE fp32 pointer; for a 1-D field also dtype_bf16: the fp32 decode rounded to
  * nearest even, torch's conversion) with libzfp 0.5.5 semantics. Fixed-rate streams
  * (minbits == maxbits) decode one block per thread; variable-rate streams need the index written by
